@@ -1,8 +1,12 @@
 #!/usr/bin/env python3
 """Headline benchmark: denoised 32 ms frames/s (16 kHz, n_fft 1024, hop 512, 80 mels) at batch 256 per GPU.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run sets up, pre-warms, runs W warm-up and K timed steps and prints one JSON line (`metric`, `value`, `unit`, `higher_is_better`,
+`dtype`, `ms_per_step`, the configuration); `--dump-outputs DIR` also writes what the last timed launch computed (float32 .npy, identical
+inputs for identical arguments).  Everything else below is measured only with `--full`.
 
 `python bench.py --gpus N` with N > 1 and no WORLD_SIZE in the environment starts the N ranks itself (a torchrun child
 process, started before this process touches the GPU) and fails loudly when the node has fewer than N GPUs.
@@ -11,13 +15,13 @@ A "step" is one pass of the whole per-hop path (P1..P12 of SURVEY.md section 8a:
 3-column STFT, mel, log1p, GRUUNet2 x3 steps, residual, expm1, inverse mel, 32-iteration Griffin-Lim,
 `* peak`) over one batch of 256 synthetic frames per GPU, inputs resident in HBM, hidden state carried
 from step to step.  Streams are independent, so N GPUs run N x 256 streams with no data-path collective
-(weak scaling); the only collectives of the headline are the barriers and the MAX of the elapsed time.  With N > 1 the
-same run also times the ingress-inclusive variant SURVEY.md section 8e asks for: rank 0 holds all N x 256 frames, every
+(weak scaling); the only collectives of the headline are the barriers and the MAX of the elapsed time.  With N > 1 and
+`--full` the same run also times the ingress-inclusive variant SURVEY.md section 8e asks for: rank 0 holds all N x 256 frames, every
 step scatters them to the ranks and gathers the denoised frames back (RCCL grouped send/recv over xGMI, issued on a
 second HIP stream and double-buffered so hop i+1's ingress and hop i-1's egress overlap hop i's kernels); it is
 reported in `ingress_variant`, never as `value`.
 
-Besides the contract fields the JSON line carries
+With `--full`, besides the contract fields the JSON line carries
   roofline     -- the dominant kernel (hop_kernel: one launch = one hop of the batch): algorithmic FLOPs per launch /
                   its average launch duration measured with HIP events in this process, against the fp32 compute peak;
   cpu_baseline -- the CPU oracle (the reference's op sequence restated on torch-CPU, oracle/pipeline_ref.py)
@@ -664,6 +668,23 @@ def ingress_variant(dn, pipe, B, world, rank, dev, lo, steps, warmup, dist, back
             "root_output_finite": ok}
 
 
+DUMP_BYTES = 64 << 20
+
+
+def dump_outputs(dirname, out, hx):
+    """--dump-outputs: `out` (hops, B, n_fft) and `hx` (B, ...) as float32 DIR/out.npy and DIR/hx.npy.  Should they exceed DUMP_BYTES, both keep the
+    same fixed, seeded sample of the streams, whose ids go to DIR/streams.npy."""
+    arrays = {"out": out.float().cpu().numpy(), "hx": hx.float().cpu().numpy()}
+    B = arrays["hx"].shape[0]
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_BYTES:
+        keep = np.sort(np.random.default_rng(0).choice(B, B * (DUMP_BYTES // 2) // total, replace=False))
+        arrays = {"out": arrays["out"][:, keep], "hx": arrays["hx"][keep], "streams": keep.astype(np.float64)}
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(dirname, f"{name}.npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -684,8 +705,16 @@ def main():
                                                             "(4 up to 384 streams, 2 below 1,024, else 1); 1 = output after the next hop.  Used when --group is 0")
     ap.add_argument("--group", type=int, default=-1, help="hops of every stream per launch (dn_pipe_set_group, 0..4: whole Griffin-Lim chains, nothing parked "
                                                             "between launches); -1 = the throughput default (4 up to 384 streams); 0 = one hop per launch (--depth)")
-    ap.add_argument("--no-extras", action="store_true", help="skip the bounded side measurements carried in the line (config 3, config 5, R1, batch-1 latency)")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the bounded side measurements carried in the line (config 3, config 5, R1, "
+                                                              "batch-1 latency)")
+    ap.add_argument("--full", action="store_true", help="after the headline, also measure what surrounds it: the ingress variant (N > 1), the serial and "
+                                                         "one-hop-per-launch schedules, stage kernels, roofline, side measurements and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps write what the timed path computed in its last launch as DIR/<name>.npy "
+                                                          "(float32): out = the denoised frames of that launch's hops (the last step last), hx = the "
+                                                          "carried hidden state after it; rank 0's streams")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     rehearsal = os.environ.get("DN_BENCH_REHEARSAL") == "1"
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -727,6 +756,8 @@ def main():
     B = args.batch
     dn = Rehearsal() if rehearsal else build_denoiser(dev, args.preset, args.conv)
     if on_gpu and (args.preset != "S" or args.stream or args.pcie or (B != BATCH and world == 1)):
+        if args.dump_outputs:
+            raise SystemExit("--dump-outputs writes the headline path's outputs; this is a side measurement")
         return side_measurement(args, dn, B, dev)
     lo, hi = shard_range(B * world, world, rank)          # this rank's global stream ids
     g = torch.Generator().manual_seed(1234 + rank)
@@ -735,25 +766,32 @@ def main():
     # WHOLE Griffin-Lim chains of the hops the previous launch fronted, one wavefront each.  A "step" stays what it was: one hop (256 frames per
     # GPU); K steps are K / group launches.  --group 0: one launch per hop (the deep pipe of round 3, --depth).
     depth, group = 1, 0
-    if rehearsal:
-        pipe = dn.pipe(B)
-    else:
+    if not rehearsal:
         from audio_denoising_amd.pipeline import HopPipeline
-        pipe = None if args.serial else HopPipeline(dn, B)
-        if pipe is not None:
+        if not args.serial:
             group = args.group if args.group >= 0 else default_group(B, N_FFT)
-            if group > 0:
-                pipe.set_group(group)
-            else:
+            if group <= 0:
                 depth = args.depth if args.depth > 0 else default_depth(B, N_FFT)
-                pipe.set_depth(depth)
+
+    def make_pipe():
+        if rehearsal:
+            return dn.pipe(B)
+        if args.serial:
+            return None
+        p = HopPipeline(dn, B)
+        if group > 0:
+            p.set_group(group)
+        else:
+            p.set_depth(depth)
+        return p
+    pipe = make_pipe()
     G = max(group, 1)
     # every hop of a group is a different batch of 256 synthetic frames (a launch reads G x 256 frames)
     frames = (0.1 * torch.randn(G, B, N_FFT, generator=g)).to(dev if on_gpu else "cpu")
     hx = dn.init_hx(B)
     out = torch.empty_like(frames)
 
-    def advance(n):
+    def advance(n, pipe=pipe, hx=hx, out=out):
         """n hops of work for every stream"""
         if pipe is None:
             for i in range(n):
@@ -779,11 +817,20 @@ def main():
         sync()
 
     # untimed: bring the GPU out of its idle power state first (a cold start ran the first few hundred hops at roughly
-    # half clock: 124 us/step instead of 68), then the W warm-up steps of the contract
-    t_pre = time.perf_counter()
-    while on_gpu and time.perf_counter() - t_pre < 0.5:
-        advance(48)
+    # half clock: 124 us/step instead of 68), then the W warm-up steps of the contract.  The pre-warm runs as many hops as fit in
+    # its time, so it runs them on a pipe and hx of its own: the timed pipe's state (hx, the frame index its Griffin-Lim seeds
+    # follow) then depends on W and K alone, and --dump-outputs writes the same arrays run after run
+    if on_gpu:
+        pre_pipe, pre_hx = make_pipe(), dn.init_hx(B)
+        pre_out = torch.empty_like(out)
+        t_pre = time.perf_counter()
+        while time.perf_counter() - t_pre < 0.5:
+            advance(48, pre_pipe, pre_hx, pre_out)
+            sync()
+        if pre_pipe is not None:
+            pre_pipe.flush()
         sync()
+        del pre_pipe, pre_hx, pre_out
     # Throughput is a steady-state quantity: the pipe stays PRIMED across both boundaries of the timed region (the hops in flight -- one group, or
     # `depth` hops -- are neither drained before t0 nor after the last step), so the launches between the two barrier + synchronize brackets are K
     # hops of work for every stream -- K front halves and K whole chains -- and nothing else.  The drain is timed right after and reported beside
@@ -805,9 +852,12 @@ def main():
     assert torch.isfinite(out).all()
     if rank == 0:
         print(f"[bench] {args.steps} steps x {B * world} frames in {elapsed:.4f} s", file=sys.stderr, flush=True)
+        if args.dump_outputs:
+            last = args.steps - (args.steps - 1) // G * G          # hops of the last launch (the drain above completed them)
+            dump_outputs(args.dump_outputs, out[:last], hx)
 
     ingress = None
-    if (world > 1 or force_dist) and pipe is not None:
+    if args.full and (world > 1 or force_dist) and pipe is not None:
         # a side measurement must never cost the headline line: any failure in it (on every rank alike: the loop is collective) is reported, not raised
         try:
             # the headline's schedule: one launch = `group` hops (its double buffering needs only that launch i completes the unit launch i-1 fronted)
@@ -846,7 +896,7 @@ def main():
             line["ingress_ok"] = "error" not in ingress and bool(ingress.get("root_output_finite", False))
         line["ranks"] = {"seen": ranks_seen, "backend": backend if (world > 1 or force_dist) else None,
                          "rank0_device": (torch.cuda.get_device_name(dev) if on_gpu else "cpu"), "local_rank": local}
-    if rank == 0 and on_gpu:
+    if args.full and rank == 0 and on_gpu:
         # the same K steps strictly one after another, nothing overlapped (dn_process_frame: one launch, no added hop of latency)
         f0, o0 = frames[0], out[0]
         torch.cuda.synchronize()

@@ -17,7 +17,7 @@ def _run(args, env_extra, timeout=300):
 
 
 def test_bench_self_launches_two_gloo_ranks_and_reports_both_ingress_variants():
-    r = _run(["--gpus", "2", "--steps", "4", "--warmup", "1", "--batch", "6"], {"DN_BENCH_REHEARSAL": "1", "DN_DIST_BACKEND": "gloo"})
+    r = _run(["--gpus", "2", "--steps", "4", "--warmup", "1", "--batch", "6", "--full"], {"DN_BENCH_REHEARSAL": "1", "DN_DIST_BACKEND": "gloo"})
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1                                   # rank 0 prints ONE JSON line
@@ -32,7 +32,7 @@ def test_bench_self_launches_two_gloo_ranks_and_reports_both_ingress_variants():
 
 def test_bench_ingress_variant_runs_the_headlines_hop_groups_on_two_gloo_ranks():
     """The scatter -> launch -> gather loop in units of four hops per launch (the headline's schedule since round 4), rank plumbing only."""
-    r = _run(["--gpus", "2", "--steps", "8", "--warmup", "1", "--batch", "5"], {"DN_BENCH_REHEARSAL": "1", "DN_DIST_BACKEND": "gloo", "DN_REHEARSAL_GROUP": "4"})
+    r = _run(["--gpus", "2", "--steps", "8", "--warmup", "1", "--batch", "5", "--full"], {"DN_BENCH_REHEARSAL": "1", "DN_DIST_BACKEND": "gloo", "DN_REHEARSAL_GROUP": "4"})
     assert r.returncode == 0, r.stderr[-2000:]
     d = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][0])
     iv = d["ingress_variant"]
@@ -51,3 +51,26 @@ def test_bench_needs_a_gpu_outside_rehearsal():
     import torch
     if not torch.cuda.is_available():
         assert r.returncode != 0 and "needs a GPU" in r.stderr
+
+
+def test_bench_plain_run_is_the_headline_alone_and_dumps_its_last_launch(tmp_path):
+    """A plain run prints the contract fields and none of what `--full` adds; `--steps` is the number of timed steps; `--dump-outputs` writes the
+    last launch's frames (the rehearsal hop's 2 * frames of the seeded input) and hx as float32, the same bits for the same arguments."""
+    import numpy as np
+    import torch
+    dumps = []
+    for run in ("a", "b"):
+        r = _run(["--gpus", "1", "--steps", "5", "--warmup", "1", "--batch", "3", "--dump-outputs", str(tmp_path / run)],
+                 {"DN_BENCH_REHEARSAL": "1", "DN_DIST_BACKEND": "gloo"})
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+        assert len(lines) == 1
+        d = json.loads(lines[0])
+        assert d["steps"] == 5 and "5 steps" in r.stderr and d["unit"] == "frames/s" and d["higher_is_better"] is True and d["dtype"] == "f32"
+        assert d["value"] > 0 and isinstance(d["ms_per_step"], float) and d["metric"]
+        assert not {"roofline", "kernel_ms", "serial_ms_per_step", "cpu_baseline", "ingress_variant", "config3_bf16"} & set(d)
+        dumps.append({k: np.load(tmp_path / run / f"{k}.npy") for k in ("out", "hx")})
+    frames = 0.1 * torch.randn(1, 3, 1024, generator=torch.Generator().manual_seed(1234))
+    assert dumps[0]["out"].dtype == np.float32 and dumps[0]["hx"].dtype == np.float32
+    assert np.array_equal(dumps[0]["out"], 2 * frames.numpy()) and dumps[0]["hx"].shape == (3, 17, 5)
+    assert all(np.array_equal(dumps[0][k], dumps[1][k]) for k in dumps[0])

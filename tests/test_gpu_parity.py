@@ -906,7 +906,7 @@ def test_bench_two_ranks_on_one_gpu(dev):
     env = dict(os.environ, DN_DIST_BACKEND="gloo", DN_ALLOW_SHARED_GPU="1")
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):
         env.pop(k, None)
-    r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "2", "--steps", "6", "--warmup", "2", "--no-cpu-baseline"],
+    r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "2", "--steps", "6", "--warmup", "2", "--no-cpu-baseline", "--full"],
                        capture_output=True, text=True, env=env, timeout=600, cwd=REPO)
     assert r.returncode == 0, r.stderr[-3000:]
     d = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
@@ -933,7 +933,7 @@ def test_bench_one_rank_over_rccl_runs_every_collective_call(dev):
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):
         env.pop(k, None)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=1", "--master-addr", "127.0.0.1", "--master-port", str(port),
-           os.path.join(REPO, "bench.py"), "--gpus", "1", "--steps", "8", "--warmup", "4", "--no-cpu-baseline", "--no-extras"]
+           os.path.join(REPO, "bench.py"), "--gpus", "1", "--steps", "8", "--warmup", "4", "--no-cpu-baseline", "--no-extras", "--full"]
     r = subprocess.run(cmd, capture_output=True, text=True, env=env, timeout=600, cwd=REPO)
     assert r.returncode == 0, r.stderr[-3000:]
     d = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
@@ -941,6 +941,29 @@ def test_bench_one_rank_over_rccl_runs_every_collective_call(dev):
     iv = d["ingress_variant"]
     assert "error" not in iv, iv
     assert d["ingress_ok"] is True and iv["backend"] == "nccl" and iv["hops_per_launch"] == 4 and iv["root_output_finite"] is True
+
+
+def test_bench_dump_outputs_are_the_same_run_after_run(dev, tmp_path):
+    """A plain `bench.py --dump-outputs DIR` on the headline's schedule (hop groups of four, batch 256): two runs with the same arguments write the
+    same bits although their time-bounded pre-warms run different numbers of hops; the arrays are the last launch's frames and the carried hx."""
+    import json
+    import subprocess
+    import sys
+    from conftest import REPO
+    env = dict(os.environ)
+    for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):
+        env.pop(k, None)
+    dumps = []
+    for run in ("a", "b"):
+        r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "1", "--steps", "10", "--warmup", "3", "--dump-outputs",
+                            str(tmp_path / run)], capture_output=True, text=True, env=env, timeout=600, cwd=REPO)
+        assert r.returncode == 0, r.stderr[-3000:]
+        d = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
+        assert d["steps"] == 10 and d["value"] > 0 and d["ms_per_step"] > 0 and d["config"]["hops_per_launch"] == 4 and "roofline" not in d
+        dumps.append({k: np.load(tmp_path / run / f"{k}.npy") for k in ("out", "hx")})
+    assert dumps[0]["out"].shape == (2, 256, 1024) and dumps[0]["hx"].shape == (256, 17, 5)          # 10 steps = launches of 4, 4, 2 hops
+    assert np.isfinite(dumps[0]["out"]).all() and np.abs(dumps[0]["out"]).max() > 0
+    assert all(np.array_equal(dumps[0][k], dumps[1][k]) for k in dumps[0])
 
 
 def test_real_clip_3s_batch1_streams_match_oracle_golden(dev):

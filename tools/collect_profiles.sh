@@ -23,7 +23,7 @@ run() {
   "$@" >> "$dst" 2>> "$out/logs/$name.log" || die "$name failed (rc $?): see $out/logs/$name.log"
   [ -s "$dst" ] || die "$name printed nothing: see $out/logs/$name.log"
 }
-python bench.py > "$out/${tag}_bench.json" 2> "$out/logs/bench.log" || die "bench.py failed"
+python bench.py --full > "$out/${tag}_bench.json" 2> "$out/logs/bench.log" || die "bench.py failed"
 echo bench
 : > "$out/${tag}_group_timelines.txt"
 run group_probe "$out/${tag}_group_timelines.txt" python tools/group_probe.py 256 4
@@ -44,7 +44,7 @@ if [ -z "$quick" ]; then
   echo side
 fi
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --stats -d "$out/kt" -o kt --output-format csv -- python3 "$root/bench.py" --steps 200 --warmup 20 --no-cpu-baseline --no-extras > "$out/logs/kt.log" 2>&1 || die "kernel trace failed"
+rocprofv3 --kernel-trace --stats -d "$out/kt" -o kt --output-format csv -- python3 "$root/bench.py" --steps 200 --warmup 20 --full --no-cpu-baseline --no-extras > "$out/logs/kt.log" 2>&1 || die "kernel trace failed"
 find "$out/kt" -name "*kernel_stats.csv" -exec cp {} "$out/${tag}_kernel_stats.csv" \;
 [ -s "$out/${tag}_kernel_stats.csv" ] || die "no kernel statistics"
 echo trace

@@ -1,7 +1,7 @@
 #!/bin/bash
 # Sweep the Griffin-Lim head start of the one-hop pipe (DN_GL_HEAD_START = iterations the front workgroup runs of its own frame's chain) on the bench workloads.
 cd "$(dirname "$0")/.."
-line() { python bench.py --no-cpu-baseline --no-extras --depth 1 "$@" 2>/dev/null | tail -1; }
+line() { python bench.py --full --no-cpu-baseline --no-extras --depth 1 "$@" 2>/dev/null | tail -1; }
 for s in 0 4 6 7 8 9 10; do
   DN_GL_HEAD_START=$s line --steps 400 | python -c "
 import sys, json

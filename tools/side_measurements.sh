@@ -1,7 +1,7 @@
 #!/bin/bash
 # The side measurements quoted in DESIGN.md / profiles/README.md, one JSON line each (tools/side_measurements.sh > profiles/rNN_side_measurements.jsonl)
 cd "$(dirname "$0")/.."
-run() { python bench.py --no-cpu-baseline --no-extras "$@" 2>/dev/null | tail -1; }
+run() { python bench.py --full --no-cpu-baseline --no-extras "$@" 2>/dev/null | tail -1; }
 run                                   # the metric's configuration (batch 256, frame mode, hop groups of four: whole Griffin-Lim chains per launch)
 run --group 2                         # groups of two hops
 run --group 0                         # one launch per hop: the deep pipe of round 3 at its default depth 4 (chain segments parked between launches)
