@@ -6,3 +6,11 @@ behind the C ABI of ``include/dn_denoise.h`` (``lib/libdn_denoise.so``).  Import
 ``from gruunet2 import GRUUNet2`` (app3.py:38), through the repo-root ``gruunet2.py``.
 """
 __version__ = "0.1.0"
+
+
+def __getattr__(name):
+    # ``audio_denoising_amd.SessionPool`` (sessions.py), imported on first use: importing the package stays free of torch
+    if name == "SessionPool":
+        import importlib
+        return importlib.import_module(__name__ + ".sessions").SessionPool
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -27,6 +27,8 @@ SYMBOLS = (
     "dn_pipe_create", "dn_pipe_destroy", "dn_pipe_set_model", "dn_pipe_set_head_start", "dn_pipe_set_gl_schedule", "dn_pipe_set_split", "dn_pipe_set_depth", "dn_pipe_set_group", "dn_pipe_submit_group", "dn_pipe_stream_push_group", "dn_pipe_stream_flush_group", "dn_pipe_reserve_parity", "dn_pipe_get_counters", "dn_pipe_submit", "dn_pipe_flush", "dn_pipe_stream_create", "dn_pipe_stream_push",
     "dn_pipe_stream_flush", "dn_pipe_stream_push_host", "dn_pipe_stream_host_wait", "dn_pipe_stream_get_state", "dn_pipe_stream_set_state", "dn_momo_create", "dn_momo_destroy",
     "dn_momo_forward", "dn_last_error", "dn_abi_version",
+    "dn_sessions_create", "dn_sessions_destroy", "dn_sessions_open", "dn_sessions_close", "dn_sessions_push", "dn_sessions_set_schedule",
+    "dn_sessions_get_counters",
 )
 
 DN_PEAK_NORMALIZE = 1
@@ -36,7 +38,8 @@ DN_GL_AUTO, DN_GL_WAVE_PER_COLUMN, DN_GL_WAVE_PER_STREAM = 0, 1, 2
 DN_HOST_STAGED = 1
 DN_HOST_DEFER = 2
 DN_SPLIT_AUTO, DN_SPLIT_OFF, DN_SPLIT_ON = -1, 0, 1
-ABI_VERSION = 4
+DN_SESS_AUTO, DN_SESS_ONE_LAUNCH, DN_SESS_TWO_LAUNCHES = 0, 1, 2
+ABI_VERSION = 5
 
 
 class ModelCfg(C.Structure):
@@ -127,6 +130,14 @@ class DnLib:
         L.dn_pipe_stream_host_wait.argtypes = [vp, u64]
         L.dn_pipe_stream_get_state.argtypes = [vp, p, p, p, vp]
         L.dn_pipe_stream_set_state.argtypes = [vp, p, p, p, u64, vp]
+        L.dn_sessions_create.argtypes = [vp, vp, i32, u32, C.POINTER(vp)]
+        L.dn_sessions_destroy.argtypes = [vp]
+        L.dn_sessions_destroy.restype = None
+        L.dn_sessions_open.argtypes = [vp, p, i32, p, vp]
+        L.dn_sessions_close.argtypes = [vp, p, i32]
+        L.dn_sessions_push.argtypes = [vp, p, i32, p, i32, p, i32, p, u64, i32, f32, vp]
+        L.dn_sessions_set_schedule.argtypes = [vp, i32]
+        L.dn_sessions_get_counters.argtypes = [vp, i32, C.POINTER(u64), C.POINTER(i32), vp]
         if L.dn_abi_version() != ABI_VERSION:
             raise ImportError(f"{path}: ABI version {L.dn_abi_version()} != {ABI_VERSION}; rebuild the extension")
 

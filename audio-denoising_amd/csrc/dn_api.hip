@@ -1481,3 +1481,240 @@ int dn_pipe_stream_flush_group(dn_pipe* p, void* hop_out, int64_t out_stride, in
 }
 
 }  // extern "C"
+
+// ------------------------------------------------------------------ session pools (dn_sessions.hip)
+// DN_SESS_AUTO: two launches (front halves, then a wavefront per chain) from this many listed slots per push on, n_fft 1024 (measured: DESIGN.md)
+static constexpr int kSessSplitAuto = 1024;
+
+struct dn_sessions {
+    dn_model* m = nullptr;
+    dn_dsp* d = nullptr;
+    BiasSet* bs = nullptr;
+    int cap = 0, C = 0;
+    bool bf16 = false;
+    int schedule = DN_SESS_AUTO;
+    // per-slot state [cap][...], and the per-row workspace of a push (rows in list order)
+    float* ring = nullptr;
+    float* ola = nullptr;
+    float* hx = nullptr;
+    unsigned long long* counters = nullptr;   // frames [cap] | stream ids [cap] | pushes [cap] (u32)
+    float* ws = nullptr;                      // mel [cap][3][M] | residual [cap][3][M] | lin [cap][3][K] | peak [cap] | meta [cap][kSessMeta]
+    std::vector<char> open;                   // host bookkeeping: which slots are open
+    // the id lists (and the stream ids of an open) on their way to the kernels: kRing entries of a page-locked staging ring, entry k reused only
+    // after the event recorded behind the last launch that read it has completed
+    static constexpr int kRing = 4;
+    char* stage_host = nullptr;
+    char* stage_dev = nullptr;                // the device's view of the entries: a device ring (DN_SESS_IDS_COPY) or the pinned one's mapping
+    size_t stage_bytes = 0;                   // one entry: ids [cap] i32, then stream ids [cap] u64 (8-byte aligned)
+    hipEvent_t ev[kRing] = {};
+    bool ev_live[kRing] = {};
+    unsigned long long calls = 0;
+    std::vector<char> seen;                   // scratch of the duplicate check
+};
+
+namespace {
+
+dn::SessArgs sess_args(dn_sessions* s) {
+    dn::SessArgs a{};
+    const int M = s->d->cfg.n_mels, K = s->d->cfg.n_fft / 2 + 1;
+    const size_t cap = (size_t)s->cap;
+    a.ring = s->ring; a.ola = s->ola; a.hx = s->hx;
+    a.frames = s->counters; a.sids = s->counters + cap; a.pushes = reinterpret_cast<unsigned int*>(s->counters + 2 * cap);
+    a.prime = s->d->cfg.n_fft / s->d->cfg.hop - 1;
+    a.mel = s->ws; a.diff = a.mel + cap * 3 * M; a.lin = a.diff + cap * 3 * M; a.peak = a.lin + cap * 3 * K;
+    a.meta = reinterpret_cast<uint32_t*>(a.peak + cap);
+    a.C = s->C;
+    return a;
+}
+
+// every id in range, none twice, and (need_open) every slot open; nothing is changed on failure
+int sess_check_ids(dn_sessions* s, const char* who, const int32_t* ids, int32_t n, bool need_open) {
+    if (n < 0) return fail(DN_ERR_INVALID, std::string(who) + ": negative count");
+    if (n > s->cap) return fail(DN_ERR_INVALID, std::string(who) + ": " + std::to_string(n) + " ids for a pool of " + std::to_string(s->cap) + " slots");
+    if (n > 0 && !ids) return fail(DN_ERR_INVALID, std::string(who) + ": null id list");
+    int rc = DN_OK;
+    int32_t i = 0;
+    for (; i < n; ++i) {
+        const int32_t id = ids[i];
+        if (id < 0 || id >= s->cap) { rc = fail(DN_ERR_INVALID, std::string(who) + ": id " + std::to_string(id) + " (position " + std::to_string(i) + ") is out of range [0, " + std::to_string(s->cap) + ")"); break; }
+        if (s->seen[id]) { rc = fail(DN_ERR_INVALID, std::string(who) + ": id " + std::to_string(id) + " appears twice in the list"); break; }
+        if (need_open && !s->open[id]) { rc = fail(DN_ERR_INVALID, std::string(who) + ": slot " + std::to_string(id) + " is not open"); break; }
+        s->seen[id] = 1;
+    }
+    for (int32_t j = 0; j < i; ++j) s->seen[ids[j]] = 0;
+    return rc;
+}
+
+// the next staging entry, free again: its event (recorded behind the last launch that read it) has completed.  The kernels read the entry
+// straight from page-locked host memory (one 4-byte load per workgroup; measured: a copy to the device ahead of the launch cost small ticks
+// 5-9 us); DN_SESS_IDS_COPY builds the copying form.
+int sess_stage(dn_sessions* s, const int32_t* ids, int32_t n, const uint64_t* sids, hipStream_t st, dn::SessArgs& a, const uint64_t** sids_dev) {
+    const int k = (int)(s->calls % dn_sessions::kRing);
+    if (s->ev_live[k]) DN_HIP(hipEventSynchronize(s->ev[k]));
+    char* h = s->stage_host + (size_t)k * s->stage_bytes;
+    char* dv = s->stage_dev + (size_t)k * s->stage_bytes;
+    const size_t sid_off = ((size_t)s->cap * sizeof(int32_t) + 7) & ~size_t(7);
+    memcpy(h, ids, (size_t)n * sizeof(int32_t));
+    if (sids_dev) {
+        uint64_t* hs = reinterpret_cast<uint64_t*>(h + sid_off);
+        for (int32_t i = 0; i < n; ++i) hs[i] = sids ? sids[i] : (uint64_t)ids[i];
+        *sids_dev = reinterpret_cast<const uint64_t*>(dv + sid_off);
+    }
+#ifdef DN_SESS_IDS_COPY
+    DN_HIP(hipMemcpyAsync(dv, h, sids_dev ? sid_off + (size_t)n * sizeof(uint64_t) : (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, st));
+#else
+    (void)st;
+#endif
+    a.ids = reinterpret_cast<const int32_t*>(dv);
+    a.n = n;
+    return DN_OK;
+}
+
+int sess_staged(dn_sessions* s, hipStream_t st) {
+    const int k = (int)(s->calls % dn_sessions::kRing);
+    DN_HIP(hipEventRecord(s->ev[k], st));
+    s->ev_live[k] = true;
+    ++s->calls;
+    return DN_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+void dn_sessions_destroy(dn_sessions* s) {
+    if (!s) return;
+    for (int k = 0; k < dn_sessions::kRing; ++k)
+        if (s->ev[k]) {
+            if (s->ev_live[k]) (void)hipEventSynchronize(s->ev[k]);
+            (void)hipEventDestroy(s->ev[k]);
+        }
+    if (s->stage_host) (void)hipHostFree(s->stage_host);
+#ifdef DN_SESS_IDS_COPY
+    if (s->stage_dev) (void)hipFree(s->stage_dev);
+#endif
+    if (s->ring) (void)hipFree(s->ring);
+    if (s->ola) (void)hipFree(s->ola);
+    if (s->hx) (void)hipFree(s->hx);
+    if (s->counters) (void)hipFree(s->counters);
+    if (s->ws) (void)hipFree(s->ws);
+    if (s->m) model_release(s->m);
+    if (s->d) dsp_release(s->d);
+    delete s;
+}
+
+int dn_sessions_create(const dn_model* m, const dn_dsp* d, int32_t capacity, uint32_t flags, dn_sessions** out) {
+    if (!out) return fail(DN_ERR_INVALID, "dn_sessions_create: null argument");
+    if (capacity <= 0) return fail(DN_ERR_INVALID, "dn_sessions_create: capacity must be positive");
+    int rc = check_hop_args("dn_sessions_create", m, d, capacity, 0, 0.0f, flags);
+    if (rc != DN_OK) return rc;
+    dn_sessions* s = new dn_sessions();
+    s->m = const_cast<dn_model*>(m); s->d = const_cast<dn_dsp*>(d);
+    s->m->refs.fetch_add(1);
+    s->d->refs.fetch_add(1);
+    s->cap = capacity; s->C = d->cfg.n_mels / 16;
+    s->bf16 = (flags & DN_CONV_BF16) != 0;
+    s->open.assign(capacity, 0);
+    s->seen.assign(capacity, 0);
+    rc = build_bias(s->m, s->C, &s->bs);
+    if (rc != DN_OK) { dn_sessions_destroy(s); return rc; }
+    const size_t cap = (size_t)capacity, N = d->cfg.n_fft, M = d->cfg.n_mels, K = N / 2 + 1;
+    const size_t line = cap * N * sizeof(float), hxb = cap * dn::kHidden * s->C * sizeof(float);
+    const size_t ws = (cap * (6 * M + 3 * K + 1) + cap * dn::kSessMeta) * sizeof(float);
+    s->stage_bytes = ((cap * sizeof(int32_t) + 7) & ~size_t(7)) + cap * sizeof(uint64_t);
+    s->stage_bytes = (s->stage_bytes + 255) & ~size_t(255);
+    hipError_t e = hipMalloc(reinterpret_cast<void**>(&s->ring), line);
+    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&s->ola), line);
+    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&s->hx), hxb);
+    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&s->counters), 3 * cap * sizeof(unsigned long long));
+    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&s->ws), ws);
+    if (e == hipSuccess) e = hipHostMalloc(reinterpret_cast<void**>(&s->stage_host), dn_sessions::kRing * s->stage_bytes, 0);
+#ifdef DN_SESS_IDS_COPY
+    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&s->stage_dev), dn_sessions::kRing * s->stage_bytes);
+#else
+    if (e == hipSuccess) e = hipHostGetDevicePointer(reinterpret_cast<void**>(&s->stage_dev), s->stage_host, 0);
+#endif
+    if (e == hipSuccess) e = hipMemset(s->ring, 0, line);
+    if (e == hipSuccess) e = hipMemset(s->ola, 0, line);
+    if (e == hipSuccess) e = hipMemset(s->hx, 0, hxb);
+    if (e == hipSuccess) e = hipMemset(s->counters, 0, 3 * cap * sizeof(unsigned long long));
+    if (e == hipSuccess) e = hipMemset(s->ws, 0, ws);
+    for (int k = 0; k < dn_sessions::kRing && e == hipSuccess; ++k) e = hipEventCreateWithFlags(&s->ev[k], hipEventDisableTiming);
+    if (e != hipSuccess) { dn_sessions_destroy(s); return fail(DN_ERR_HIP, std::string("dn_sessions_create: ") + hipGetErrorString(e)); }
+    *out = s;
+    return DN_OK;
+}
+
+int dn_sessions_open(dn_sessions* s, const int32_t* ids, int32_t n, const uint64_t* stream_ids, void* stream) {
+    if (!s) return fail(DN_ERR_INVALID, "dn_sessions_open: null pool");
+    int rc = sess_check_ids(s, "dn_sessions_open", ids, n, false);
+    if (rc != DN_OK || n == 0) return rc;
+    hipStream_t st = as_stream(stream);
+    dn::SessArgs a = sess_args(s);
+    const uint64_t* sids_dev = nullptr;
+    rc = sess_stage(s, ids, n, stream_ids, st, a, &sids_dev);
+    if (rc != DN_OK) return rc;
+    dn::launch_sess_open(a, sids_dev, s->d->cfg.n_fft, st);
+    rc = check_launch("sess_open_kernel");
+    if (rc != DN_OK) return rc;
+    for (int32_t i = 0; i < n; ++i) s->open[ids[i]] = 1;
+    return sess_staged(s, st);
+}
+
+int dn_sessions_close(dn_sessions* s, const int32_t* ids, int32_t n) {
+    if (!s) return fail(DN_ERR_INVALID, "dn_sessions_close: null pool");
+    int rc = sess_check_ids(s, "dn_sessions_close", ids, n, true);
+    if (rc != DN_OK) return rc;
+    for (int32_t i = 0; i < n; ++i) s->open[ids[i]] = 0;
+    return DN_OK;
+}
+
+int dn_sessions_set_schedule(dn_sessions* s, int32_t schedule) {
+    if (!s) return fail(DN_ERR_INVALID, "dn_sessions_set_schedule: null pool");
+    if (schedule != DN_SESS_AUTO && schedule != DN_SESS_ONE_LAUNCH && schedule != DN_SESS_TWO_LAUNCHES)
+        return fail(DN_ERR_INVALID, "dn_sessions_set_schedule: unknown schedule");
+    if (schedule == DN_SESS_TWO_LAUNCHES && s->d->cfg.n_fft != 1024)
+        return fail(DN_ERR_UNSUPPORTED, "dn_sessions_set_schedule: the two-launch form runs a wavefront per Griffin-Lim chain, which is built for n_fft 1024");
+    s->schedule = schedule;
+    return DN_OK;
+}
+
+int dn_sessions_push(dn_sessions* s, const int32_t* ids, int32_t n, const void* hop_in, int32_t in_is_s16, void* hop_out,
+                     int32_t out_is_s16, const float* init_angles, uint64_t seed, int32_t n_iter, float momentum, void* stream) {
+    // everything is validated before the first launch: a failed call leaves every slot as it was
+    if (!s) return fail(DN_ERR_INVALID, "dn_sessions_push: null pool");
+    int rc = sess_check_ids(s, "dn_sessions_push", ids, n, true);
+    if (rc != DN_OK || n == 0) return rc;
+    if (!hop_in || !hop_out) return fail(DN_ERR_INVALID, "dn_sessions_push: null argument");
+    rc = check_hop_args("dn_sessions_push", s->m, s->d, n, n_iter, momentum, 0);
+    if (rc != DN_OK) return rc;
+    hipStream_t st = as_stream(stream);
+    dn::SessArgs a = sess_args(s);
+    rc = sess_stage(s, ids, n, nullptr, st, a, nullptr);
+    if (rc != DN_OK) return rc;
+    a.hop_in = hop_in; a.in_s16 = in_is_s16 ? 1 : 0; a.hop_out = hop_out; a.out_s16 = out_is_s16 ? 1 : 0;
+    a.init = init_angles; a.seed = seed; a.n_iter = n_iter; a.mom = momentum / (1.0f + momentum);
+    const bool two = s->d->cfg.n_fft == 1024 && (s->schedule == DN_SESS_TWO_LAUNCHES || (s->schedule == DN_SESS_AUTO && n >= kSessSplitAuto));
+    if (two) dn::launch_sess_split(s->d->view, s->bs->view, a, s->bf16, st);
+    else dn::launch_sess_frame(s->d->view, s->bs->view, a, s->bf16, st);
+    rc = check_launch(two ? "sess_front_kernel / sess_chain_kernel" : "sess_frame_kernel");
+    if (rc != DN_OK) return rc;
+    return sess_staged(s, st);
+}
+
+int dn_sessions_get_counters(dn_sessions* s, int32_t id, uint64_t* frames, int32_t* pushes, void* stream) {
+    if (!s) return fail(DN_ERR_INVALID, "dn_sessions_get_counters: null pool");
+    if (id < 0 || id >= s->cap) return fail(DN_ERR_INVALID, "dn_sessions_get_counters: id out of range");
+    const dn::SessArgs a = sess_args(s);
+    unsigned long long f = 0;
+    unsigned int p = 0;
+    hipStream_t st = as_stream(stream);
+    DN_HIP(hipMemcpyAsync(&f, a.frames + id, sizeof(f), hipMemcpyDeviceToHost, st));
+    DN_HIP(hipMemcpyAsync(&p, a.pushes + id, sizeof(p), hipMemcpyDeviceToHost, st));
+    DN_HIP(hipStreamSynchronize(st));
+    if (frames) *frames = f;
+    if (pushes) *pushes = (int32_t)p;
+    return DN_OK;
+}
+
+}  // extern "C"

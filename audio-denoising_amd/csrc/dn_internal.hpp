@@ -199,6 +199,23 @@ struct FrameArgs {
     const float* hop_in; float* ring; float* ola; float* hop_out;    // dn_stream_step (ring != null)
 };
 void launch_frame(const DspDev& d, const CellDev& c, const FrameArgs& a, int B, bool bf16, hipStream_t st);
+// One hop for n listed slots of a session pool (dn_sessions.hip).  Slot-indexed: ring, ola, hx and the counters; row-indexed (list order): hop_in,
+// hop_out, init and the workspace.
+constexpr int kSessMeta = 4;      // u32 a row the front launch of the two-launch form leaves its chain: [0] runs a chain, [1,2] Griffin-Lim seed
+struct SessArgs {
+    const int32_t* ids; int n;                                  // [n] slot of row i (device copy, validated on the host)
+    float* ring; float* ola; float* hx;                         // [cap][n_fft], [cap][n_fft], [cap][17][C]
+    unsigned long long* frames; unsigned long long* sids;       // [cap] frames since the slot's open, its Griffin-Lim stream id
+    unsigned int* pushes;                                       // [cap] pushes since the open, counted up to `prime`
+    int prime;                                                  // n_fft / hop - 1: pushes that only fill the ring
+    const void* hop_in; int in_s16; void* hop_out; int out_s16; // [n][hop] float32 or int16
+    const float* init;                                          // [n][3][K] complex initial phases, or null = device RNG
+    float* mel; float* diff; float* lin; float* peak; uint32_t* meta;   // workspace rows [cap][3][M], [cap][3][M], [cap][3][K], [cap], [cap][kSessMeta]
+    uint64_t seed; int n_iter; float mom; int C;
+};
+void launch_sess_frame(const DspDev& d, const CellDev& c, const SessArgs& a, bool bf16, hipStream_t st);
+void launch_sess_split(const DspDev& d, const CellDev& c, const SessArgs& a, bool bf16, hipStream_t st);     // n_fft 1024
+void launch_sess_open(const SessArgs& a, const uint64_t* sids_in, int n_fft, hipStream_t st);
 void launch_cell_bf16(const CellDev& c, const float* x, const float* hx_in, float* out, float* hx_out, int B, int T,
                       int C, hipStream_t st);
 void launch_cell_ex(const CellDev& c, const float* x, const float* hx_in, float* out, float* hx_out, int B, int T,

@@ -26,6 +26,8 @@
  *   dn_stft_general / dn_server_rows / dn_istft_general / dn_cell_forward_ex   server.py:199-217  the socket server's variant
  *   dn_process_frame                    app3.py:178-217  the whole per-hop loop body for B streams
  *   dn_stream_step                      app3.py:178-226  the same plus ring buffer / overlap-add state (P12)
+ *   dn_sessions_*                       app3.py:123-250  one DenoisingAudioProcessor per session: slots that join, leave
+ *                                       and push hops on their own, batched per tick
  *   dn_pipe_*                           app3.py:167-250  the same hop, consecutive hops software-pipelined in one launch per hop
  *                                       (dn_pipe_stream_*: the steady-state recv loop with its per-stream buffers)
  *
@@ -51,7 +53,7 @@
 extern "C" {
 #endif
 
-#define DN_ABI_VERSION 4
+#define DN_ABI_VERSION 5
 
 typedef enum dn_status {
     DN_OK = 0,
@@ -372,6 +374,51 @@ int dn_pipe_stream_host_wait(dn_pipe* p, uint64_t ticket);
 int dn_pipe_stream_get_state(dn_pipe* p, float* ring, float* ola, float* hx, void* stream);
 int dn_pipe_stream_set_state(dn_pipe* p, const float* ring, const float* ola, const float* hx, uint64_t frames_done,
                              void* stream);
+
+/* ---- Session pools: streams that join, leave and push hops on their own ------------------------------
+ * Every interface above advances ALL B streams of a batch by the same hop.  A session pool holds `capacity` stream slots
+ * instead, each with its own state in HBM, owned by the library: ring [cap][n_fft], overlap-add line [cap][n_fft],
+ * hx [cap][17][C], a frame counter, a priming count and a Griffin-Lim stream id.  One push runs one hop for a LIST of
+ * slots -- any subset, in any order -- and leaves every other slot exactly as it was: one WebRTC session per slot
+ * (app3.py:123-133), each of whose recv() calls runs 0, 1 or 2 hops (app3.py:167-178), batched onto the GPU tick by tick.
+ *
+ *   dn_sessions_open   (re)opens n slots: ring, ola and hx zeroed, frame and priming counts 0, Griffin-Lim stream id
+ *                      stream_ids[i] (stream_ids NULL: the slot index).  Enqueued on `stream`.
+ *   dn_sessions_close  closes n slots (host bookkeeping only: a closed slot may not be pushed until it is opened again).
+ *   dn_sessions_push   one hop for each of the n listed slots.  ids [host][n]; the rows of hop_in [dev][n][hop],
+ *                      hop_out [dev][n][hop] and init_angles [dev][n][3][K] complex (NULL: device RNG) are in LIST order.
+ *                      in_is_s16 / out_is_s16 as dn_pipe_stream_push (x / 32767 in; clip, * 32767, truncate out).
+ *                      A slot's first n_fft/hop - 1 pushes only shift its ring and emit a zero row; after that every push
+ *                      runs one frame with no added latency and emits ola[:hop] before the frame is added (app3.py:219-224),
+ *                      exactly as dn_stream_step.  The slot's f-th frame (f counted from its open) draws its phases from
+ *                      (seed + f, its stream id): a session's samples do not depend on which other slots share a push.
+ *
+ * The id lists are validated on the HOST before anything is enqueued: every id in [0, capacity), none twice, and (push,
+ * close) every slot open.  A bad list returns DN_ERR_INVALID and leaves all state as it was.  The library moves the ids to
+ * the device itself (a page-locked staging ring guarded by events): the caller may reuse its array once the call returns.
+ * Consecutive calls on one pool are ordered by `stream`: use one stream per pool.
+ * NOT thread-safe (one host thread at a time per pool) and NOT capturable into a hipGraph (the list changes every tick).
+ *
+ * Schedules (dn_sessions_set_schedule):
+ *   DN_SESS_ONE_LAUNCH    one workgroup per listed slot runs P1-P12 back to back (n_fft 1024 and 1536);
+ *   DN_SESS_TWO_LAUNCHES  the front halves (P1-P10) of all listed slots, then their Griffin-Lim chains a wavefront per
+ *                         session (n_fft 1024); the same samples, bit for bit;
+ *   DN_SESS_AUTO          (default) two launches from 1,024 listed slots on at n_fft 1024 (the measured crossover: DESIGN.md 4.11).
+ * flags of dn_sessions_create: DN_CONV_BF16 or 0.  The pool holds a reference on its model and plan (as a dn_pipe). */
+typedef struct dn_sessions dn_sessions;
+#define DN_SESS_AUTO 0
+#define DN_SESS_ONE_LAUNCH 1
+#define DN_SESS_TWO_LAUNCHES 2
+int dn_sessions_create(const dn_model* m, const dn_dsp* d, int32_t capacity, uint32_t flags, dn_sessions** out);
+void dn_sessions_destroy(dn_sessions* s);
+int dn_sessions_open(dn_sessions* s, const int32_t* ids, int32_t n, const uint64_t* stream_ids, void* stream);
+int dn_sessions_close(dn_sessions* s, const int32_t* ids, int32_t n);
+int dn_sessions_push(dn_sessions* s, const int32_t* ids, int32_t n, const void* hop_in, int32_t in_is_s16, void* hop_out,
+                     int32_t out_is_s16, const float* init_angles, uint64_t seed, int32_t n_iter, float momentum, void* stream);
+int dn_sessions_set_schedule(dn_sessions* s, int32_t schedule);
+/* the slot's counters as of the last call on `stream` (synchronises it): frames run since its open, pushes counted up to
+ * n_fft/hop - 1 (primed when equal) */
+int dn_sessions_get_counters(dn_sessions* s, int32_t id, uint64_t* frames, int32_t* pushes, void* stream);
 
 const char* dn_last_error(void);
 int dn_abi_version(void);
