@@ -9,8 +9,8 @@ __version__ = "0.1.0"
 
 
 def __getattr__(name):
-    # ``audio_denoising_amd.SessionPool`` (sessions.py), imported on first use: importing the package stays free of torch
-    if name == "SessionPool":
+    # ``audio_denoising_amd.SessionPool`` / ``SessionState`` (sessions.py), imported on first use: importing the package stays free of torch
+    if name in ("SessionPool", "SessionState"):
         import importlib
-        return importlib.import_module(__name__ + ".sessions").SessionPool
+        return getattr(importlib.import_module(__name__ + ".sessions"), name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

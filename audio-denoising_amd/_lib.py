@@ -28,7 +28,7 @@ SYMBOLS = (
     "dn_pipe_stream_flush", "dn_pipe_stream_push_host", "dn_pipe_stream_host_wait", "dn_pipe_stream_get_state", "dn_pipe_stream_set_state", "dn_momo_create", "dn_momo_destroy",
     "dn_momo_forward", "dn_last_error", "dn_abi_version",
     "dn_sessions_create", "dn_sessions_destroy", "dn_sessions_open", "dn_sessions_close", "dn_sessions_push", "dn_sessions_set_schedule",
-    "dn_sessions_get_counters",
+    "dn_sessions_get_counters", "dn_sessions_record_bytes", "dn_sessions_export", "dn_sessions_import",
 )
 
 DN_PEAK_NORMALIZE = 1
@@ -39,7 +39,7 @@ DN_HOST_STAGED = 1
 DN_HOST_DEFER = 2
 DN_SPLIT_AUTO, DN_SPLIT_OFF, DN_SPLIT_ON = -1, 0, 1
 DN_SESS_AUTO, DN_SESS_ONE_LAUNCH, DN_SESS_TWO_LAUNCHES = 0, 1, 2
-ABI_VERSION = 5
+ABI_VERSION = 6
 
 
 class ModelCfg(C.Structure):
@@ -138,6 +138,10 @@ class DnLib:
         L.dn_sessions_push.argtypes = [vp, p, i32, p, i32, p, i32, p, u64, i32, f32, vp]
         L.dn_sessions_set_schedule.argtypes = [vp, i32]
         L.dn_sessions_get_counters.argtypes = [vp, i32, C.POINTER(u64), C.POINTER(i32), vp]
+        L.dn_sessions_record_bytes.argtypes = [vp]
+        L.dn_sessions_record_bytes.restype = C.c_size_t
+        L.dn_sessions_export.argtypes = [vp, p, i32, vp, vp]
+        L.dn_sessions_import.argtypes = [vp, p, i32, vp, p, vp]
         if L.dn_abi_version() != ABI_VERSION:
             raise ImportError(f"{path}: ABI version {L.dn_abi_version()} != {ABI_VERSION}; rebuild the extension")
 

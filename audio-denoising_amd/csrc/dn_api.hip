@@ -1510,6 +1510,9 @@ struct dn_sessions {
     bool ev_live[kRing] = {};
     unsigned long long calls = 0;
     std::vector<char> seen;                   // scratch of the duplicate check
+    // dn_sessions_import: the header check of each record [cap] u32, written by the device into page-locked memory, read after one synchronisation
+    uint32_t* chk_host = nullptr;
+    uint32_t* chk_dev = nullptr;
 };
 
 namespace {
@@ -1570,6 +1573,31 @@ int sess_stage(dn_sessions* s, const int32_t* ids, int32_t n, const uint64_t* si
     return DN_OK;
 }
 
+// the record geometry of a pool (include/dn_denoise.h: record layout version 1)
+dn::SessRec sess_rec(const dn_sessions* s) {
+    const dn_dsp_cfg& c = s->d->cfg;
+    const auto a16 = [](size_t x) { return (x + 15) & ~size_t(15); };
+    dn::SessRec r{};
+    r.ola_off = dn::kSessRecHead + a16((size_t)c.n_fft * sizeof(float));
+    r.hx_off = r.ola_off + a16((size_t)c.n_fft * sizeof(float));
+    r.stride = (r.hx_off + (size_t)dn::kHidden * s->C * sizeof(float) + 255) & ~size_t(255);
+    r.want.magic = DN_SESS_RECORD_MAGIC;
+    r.want.version = DN_SESS_RECORD_VERSION;
+    r.want.sample_rate = (uint32_t)c.sample_rate;
+    r.want.n_fft = (uint32_t)c.n_fft;
+    r.want.hop = (uint32_t)c.hop;
+    r.want.n_mels = (uint32_t)c.n_mels;
+    r.want.hidden = (uint32_t)dn::kHidden;
+    r.want.C = (uint32_t)s->C;
+    r.prime = (uint32_t)(c.n_fft / c.hop - 1);
+    return r;
+}
+
+std::string sess_geometry(uint32_t sr, uint32_t n_fft, uint32_t hop, uint32_t n_mels, uint32_t hidden, uint32_t C) {
+    return "sample_rate " + std::to_string(sr) + ", n_fft " + std::to_string(n_fft) + ", hop " + std::to_string(hop) + ", n_mels " +
+           std::to_string(n_mels) + ", hidden " + std::to_string(hidden) + ", C " + std::to_string(C);
+}
+
 int sess_staged(dn_sessions* s, hipStream_t st) {
     const int k = (int)(s->calls % dn_sessions::kRing);
     DN_HIP(hipEventRecord(s->ev[k], st));
@@ -1590,6 +1618,7 @@ void dn_sessions_destroy(dn_sessions* s) {
             (void)hipEventDestroy(s->ev[k]);
         }
     if (s->stage_host) (void)hipHostFree(s->stage_host);
+    if (s->chk_host) (void)hipHostFree(s->chk_host);
 #ifdef DN_SESS_IDS_COPY
     if (s->stage_dev) (void)hipFree(s->stage_dev);
 #endif
@@ -1629,6 +1658,8 @@ int dn_sessions_create(const dn_model* m, const dn_dsp* d, int32_t capacity, uin
     if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&s->counters), 3 * cap * sizeof(unsigned long long));
     if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&s->ws), ws);
     if (e == hipSuccess) e = hipHostMalloc(reinterpret_cast<void**>(&s->stage_host), dn_sessions::kRing * s->stage_bytes, 0);
+    if (e == hipSuccess) e = hipHostMalloc(reinterpret_cast<void**>(&s->chk_host), cap * sizeof(uint32_t), 0);
+    if (e == hipSuccess) e = hipHostGetDevicePointer(reinterpret_cast<void**>(&s->chk_dev), s->chk_host, 0);
 #ifdef DN_SESS_IDS_COPY
     if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&s->stage_dev), dn_sessions::kRing * s->stage_bytes);
 #else
@@ -1699,6 +1730,66 @@ int dn_sessions_push(dn_sessions* s, const int32_t* ids, int32_t n, const void* 
     else dn::launch_sess_frame(s->d->view, s->bs->view, a, s->bf16, st);
     rc = check_launch(two ? "sess_front_kernel / sess_chain_kernel" : "sess_frame_kernel");
     if (rc != DN_OK) return rc;
+    return sess_staged(s, st);
+}
+
+size_t dn_sessions_record_bytes(const dn_sessions* s) {
+    return s ? sess_rec(s).stride : 0;
+}
+
+int dn_sessions_export(dn_sessions* s, const int32_t* ids, int32_t n, void* records, void* stream) {
+    if (!s) return fail(DN_ERR_INVALID, "dn_sessions_export: null pool");
+    int rc = sess_check_ids(s, "dn_sessions_export", ids, n, true);
+    if (rc != DN_OK || n == 0) return rc;
+    if (!records) return fail(DN_ERR_INVALID, "dn_sessions_export: null records");
+    if (reinterpret_cast<uintptr_t>(records) % 16 != 0) return fail(DN_ERR_INVALID, "dn_sessions_export: records must be 16-byte aligned");
+    hipStream_t st = as_stream(stream);
+    dn::SessArgs a = sess_args(s);
+    rc = sess_stage(s, ids, n, nullptr, st, a, nullptr);
+    if (rc != DN_OK) return rc;
+    dn::launch_sess_export(a, sess_rec(s), s->d->cfg.n_fft, records, st);
+    rc = check_launch("sess_export_kernel");
+    if (rc != DN_OK) return rc;
+    return sess_staged(s, st);
+}
+
+int dn_sessions_import(dn_sessions* s, const int32_t* ids, int32_t n, const void* records, const uint64_t* stream_ids, void* stream) {
+    // ids on the host, then every record's header on the device into page-locked memory and one synchronisation: no slot changes unless all pass
+    if (!s) return fail(DN_ERR_INVALID, "dn_sessions_import: null pool");
+    int rc = sess_check_ids(s, "dn_sessions_import", ids, n, false);
+    if (rc != DN_OK || n == 0) return rc;
+    if (!records) return fail(DN_ERR_INVALID, "dn_sessions_import: null records");
+    if (reinterpret_cast<uintptr_t>(records) % 16 != 0) return fail(DN_ERR_INVALID, "dn_sessions_import: records must be 16-byte aligned");
+    hipStream_t st = as_stream(stream);
+    dn::SessArgs a = sess_args(s);
+    const uint64_t* sids_dev = nullptr;
+    rc = sess_stage(s, ids, n, stream_ids, st, a, stream_ids ? &sids_dev : nullptr);
+    if (rc != DN_OK) return rc;
+    const dn::SessRec r = sess_rec(s);
+    dn::launch_sess_check(a, r, records, s->chk_dev, st);
+    rc = check_launch("sess_check_kernel");
+    if (rc != DN_OK) return rc;
+    DN_HIP(hipStreamSynchronize(st));          // (the staging entry is free again after this: no event needed until the import launch)
+    for (int32_t i = 0; i < n; ++i) {
+        const uint32_t bad = s->chk_host[i];
+        if (bad == 0) continue;
+        std::string who = "dn_sessions_import: record " + std::to_string(i) + " (for slot " + std::to_string(ids[i]) + ")";
+        if (bad == dn::kSessRecBadMagic) return fail(DN_ERR_INVALID, who + " is not a session record (bad magic)");
+        dn_session_record_header h{};
+        DN_HIP(hipMemcpy(&h, static_cast<const char*>(records) + (size_t)i * r.stride, sizeof(h), hipMemcpyDeviceToHost));
+        if (bad == dn::kSessRecBadVersion)
+            return fail(DN_ERR_INVALID, who + " has record version " + std::to_string(h.version) + ", this library reads version " +
+                                            std::to_string(DN_SESS_RECORD_VERSION));
+        if (bad == dn::kSessRecBadGeometry)
+            return fail(DN_ERR_INVALID, who + " has geometry " + sess_geometry(h.sample_rate, h.n_fft, h.hop, h.n_mels, h.hidden, h.C) +
+                                            "; this pool's is " + sess_geometry(r.want.sample_rate, r.want.n_fft, r.want.hop, r.want.n_mels,
+                                                                                 r.want.hidden, r.want.C));
+        return fail(DN_ERR_INVALID, who + " has priming count " + std::to_string(h.pushes) + " > n_fft/hop - 1 = " + std::to_string(r.prime));
+    }
+    dn::launch_sess_import(a, r, s->d->cfg.n_fft, records, sids_dev, st);
+    rc = check_launch("sess_import_kernel");
+    if (rc != DN_OK) return rc;
+    for (int32_t i = 0; i < n; ++i) s->open[ids[i]] = 1;
     return sess_staged(s, st);
 }
 

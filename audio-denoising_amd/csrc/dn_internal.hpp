@@ -216,6 +216,19 @@ struct SessArgs {
 void launch_sess_frame(const DspDev& d, const CellDev& c, const SessArgs& a, bool bf16, hipStream_t st);
 void launch_sess_split(const DspDev& d, const CellDev& c, const SessArgs& a, bool bf16, hipStream_t st);     // n_fft 1024
 void launch_sess_open(const SessArgs& a, const uint64_t* sids_in, int n_fft, hipStream_t st);
+// Session records (dn_sessions_export / dn_sessions_import; layout: include/dn_denoise.h).  Record i of a call is records + i * stride and
+// belongs to slot ids[i].
+constexpr int kSessRecHead = 64;                                // sizeof(dn_session_record_header): the ring starts here
+struct SessRec {
+    size_t stride, ola_off, hx_off;                             // bytes: one record, the overlap-add line, hx
+    dn_session_record_header want;                              // this pool's header (magic .. C); the counters are the slot's
+    unsigned int prime;                                         // n_fft / hop - 1: the largest valid priming count
+};
+void launch_sess_export(const SessArgs& a, const SessRec& r, int n_fft, void* records, hipStream_t st);
+// status [n] (page-locked, mapped): 0 for a valid header, else kSessRecBad*
+constexpr uint32_t kSessRecBadMagic = 1, kSessRecBadVersion = 2, kSessRecBadGeometry = 3, kSessRecBadPushes = 4;
+void launch_sess_check(const SessArgs& a, const SessRec& r, const void* records, uint32_t* status, hipStream_t st);
+void launch_sess_import(const SessArgs& a, const SessRec& r, int n_fft, const void* records, const uint64_t* sids_in, hipStream_t st);
 void launch_cell_bf16(const CellDev& c, const float* x, const float* hx_in, float* out, float* hx_out, int B, int T,
                       int C, hipStream_t st);
 void launch_cell_ex(const CellDev& c, const float* x, const float* hx_in, float* out, float* hx_out, int B, int T,

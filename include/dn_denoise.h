@@ -27,7 +27,8 @@
  *   dn_process_frame                    app3.py:178-217  the whole per-hop loop body for B streams
  *   dn_stream_step                      app3.py:178-226  the same plus ring buffer / overlap-add state (P12)
  *   dn_sessions_*                       app3.py:123-250  one DenoisingAudioProcessor per session: slots that join, leave
- *                                       and push hops on their own, batched per tick
+ *                                       and push hops on their own, batched per tick; sessions exported to and
+ *                                       imported from self-contained records (move, resume, resize a pool)
  *   dn_pipe_*                           app3.py:167-250  the same hop, consecutive hops software-pipelined in one launch per hop
  *                                       (dn_pipe_stream_*: the steady-state recv loop with its per-stream buffers)
  *
@@ -53,7 +54,7 @@
 extern "C" {
 #endif
 
-#define DN_ABI_VERSION 5
+#define DN_ABI_VERSION 6
 
 typedef enum dn_status {
     DN_OK = 0,
@@ -419,6 +420,60 @@ int dn_sessions_set_schedule(dn_sessions* s, int32_t schedule);
 /* the slot's counters as of the last call on `stream` (synchronises it): frames run since its open, pushes counted up to
  * n_fft/hop - 1 (primed when equal) */
 int dn_sessions_get_counters(dn_sessions* s, int32_t id, uint64_t* frames, int32_t* pushes, void* stream);
+
+/* ---- Session records: export and import the state of sessions ---------------------------------------
+ * A session's whole state leaves its pool as one self-contained RECORD and enters any pool of the same geometry: a full
+ * pool grows (a larger pool imports every session at its slot number), a GPU is drained onto another, sessions are
+ * suspended to host memory or a file and resumed in a new process.  Continuation is bit-exact: after an import a
+ * session emits the samples it would have emitted in its old pool.
+ *
+ * Record layout, version 1 (DN_SESS_RECORD_VERSION; little-endian, offsets in bytes from the start of the record):
+ *     0  header, 64 B: dn_session_record_header below
+ *    64  ring [n_fft]   float32                      the input ring buffer (app3.py:176)
+ *   R_o  ola  [n_fft]   float32  R_o = 64 + A(4 n_fft)      the overlap-add line (app3.py:133)
+ *   H_o  hx   [17][C]   float32  H_o = R_o + A(4 n_fft)     the GRU hidden state
+ *   stride = dn_sessions_record_bytes = round_up(H_o + 4 * 17 * C, 256);  A(x) = round_up(x, 16); the rest is zero.
+ * n_fft 1024 / 80 mels: 8,704 B a record.  A list of n records is [n][stride], record i at i * stride, in device memory
+ * aligned to 16 bytes (else DN_ERR_INVALID).
+ * The header's counters are the slot's: `pushes` counts its pushes up to n_fft/hop - 1 (primed when equal), `frames`
+ * the frames run since its open (frame f draws its phases from (seed + f, stream_id)).
+ *
+ * Neither the weights nor conv_precision are recorded or checked: importing onto updated weights of the same geometry
+ * is a rolling upgrade, as dn_pipe_set_model allows for a pipe.  The seed is the caller's (an argument of every push):
+ * push with the seed of the pool that exported, or the continuation is not bit-exact.
+ *
+ *   dn_sessions_record_bytes  the stride of one record for this pool's geometry (0 for a null pool).
+ *   dn_sessions_export  writes the records of the n listed slots to records [dev][n][stride] in list order.  Every id in
+ *                       range, none twice, every slot open (checked on the host: DN_ERR_INVALID, nothing enqueued).
+ *                       Enqueued on `stream`: it sees every earlier push on that stream.  It changes nothing in the
+ *                       pool -- an exported session that keeps running gives the same bits as one never exported.
+ *   dn_sessions_import  (re)opens the n listed slots with the state of records [dev][n][stride] (record i -> slot
+ *                       ids[i]), as dn_sessions_open does; every other slot is left alone.  stream_ids [host][n]
+ *                       overrides the recorded Griffin-Lim stream ids (NULL: keep them), so the sessions of two pools do
+ *                       not collide on phase keys.  Every record is validated before any slot changes: magic, version,
+ *                       a geometry equal to this pool's (sample_rate, n_fft, hop, n_mels, hidden, C) and a priming count
+ *                       <= n_fft/hop - 1, plus the id checks of dn_sessions_open (in range, none twice).  On any failure
+ *                       it returns DN_ERR_INVALID with a message and the pool is exactly as before.
+ *                       Validation reads the headers on the host: import SYNCHRONISES `stream` (one check launch
+ *                       into page-locked memory, one synchronisation), then enqueues the copy into the slots. */
+#define DN_SESS_RECORD_MAGIC 0x52534E44u    /* "DNSR" */
+#define DN_SESS_RECORD_VERSION 1
+typedef struct dn_session_record_header {
+    uint32_t magic;          /* DN_SESS_RECORD_MAGIC */
+    uint32_t version;        /* DN_SESS_RECORD_VERSION */
+    uint32_t sample_rate, n_fft, hop, n_mels;
+    uint32_t hidden;         /* 17 */
+    uint32_t C;              /* n_mels / 16 */
+    uint32_t pushes;         /* priming count, up to n_fft/hop - 1 */
+    uint32_t reserved0;      /* 0 */
+    uint64_t frames;         /* frames since the session's open */
+    uint64_t stream_id;      /* Griffin-Lim stream id */
+    uint64_t reserved1;      /* 0 */
+} dn_session_record_header;
+size_t dn_sessions_record_bytes(const dn_sessions* s);
+int dn_sessions_export(dn_sessions* s, const int32_t* ids, int32_t n, void* records, void* stream);
+int dn_sessions_import(dn_sessions* s, const int32_t* ids, int32_t n, const void* records, const uint64_t* stream_ids,
+                       void* stream);
 
 const char* dn_last_error(void);
 int dn_abi_version(void);
