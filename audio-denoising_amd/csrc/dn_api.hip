@@ -482,8 +482,8 @@ int dn_cell_forward_bf16(const dn_model* m, const float* x, const float* hx_in, 
 
 int dn_dsp_create(const dn_dsp_cfg* cfg, const float* fb_in, const float* pinv_in, const float* window_in, dn_dsp** out) {
     if (!cfg || !out) return fail(DN_ERR_INVALID, "dn_dsp_create: null argument");
-    if ((cfg->n_fft != 1024 && cfg->n_fft != 1536) || cfg->hop != cfg->n_fft / 2)
-        return fail(DN_ERR_UNSUPPORTED, "kernels are built for n_fft 1024 or 1536 with hop = n_fft/2 (got n_fft " +
+    if ((cfg->n_fft != 512 && cfg->n_fft != 1024 && cfg->n_fft != 1536) || cfg->hop != cfg->n_fft / 2)
+        return fail(DN_ERR_UNSUPPORTED, "kernels are built for n_fft 512, 1024 or 1536 with hop = n_fft/2 (got n_fft " +
                                             std::to_string(cfg->n_fft) + ", hop " + std::to_string(cfg->hop) + ")");
     const int N = cfg->n_fft, K = N / 2 + 1, M = cfg->n_mels;
     if (M < 0 || M > 128) return fail(DN_ERR_UNSUPPORTED, "n_mels must be in 0..128");
@@ -886,7 +886,7 @@ static size_t slot_floats(const dn_dsp* d, int32_t B) {
     return (size_t)B * (6 * (size_t)d->cfg.n_mels + 1 + dn::kSlotMeta + 3 * ((size_t)d->cfg.n_fft / 2 + 1));
 }
 
-// the head start a one-hop pipe runs with unless told otherwise (measured optima; none above 256 streams, none on a deep pipe)
+// the head start a one-hop pipe runs with unless told otherwise (measured optima; n_fft 512 takes 1024's, not swept yet; none above 256 streams, none on a deep pipe)
 static int default_head_start(const dn_pipe* p) {
     return p->depth == 1 && p->B <= 256 ? (p->d->cfg.n_fft == 1536 ? 12 : 8) : 0;
 }
@@ -973,7 +973,7 @@ int dn_pipe_set_depth(dn_pipe* p, int32_t depth) {
     if (!p) return fail(DN_ERR_INVALID, "dn_pipe_set_depth: null pipe");
     if (depth < 1 || depth > DN_PIPE_MAX_DEPTH) return fail(DN_ERR_INVALID, "dn_pipe_set_depth: depth must be in 1.." + std::to_string(DN_PIPE_MAX_DEPTH));
     if (depth > 1 && p->d->cfg.n_fft != 1024)
-        return fail(DN_ERR_UNSUPPORTED, "pipes deeper than one hop are built for n_fft 1024 (at 1536 the per-lane state of a stream does not fit a wavefront's registers)");
+        return fail(DN_ERR_UNSUPPORTED, "pipes deeper than one hop are built for n_fft 1024 (at 1536 the per-lane state of a stream does not fit a wavefront's registers; at 512 the schedule is not built)");
     if (depth > 1 && p->group > 0) return fail(DN_ERR_INVALID, "dn_pipe_set_depth: a group pipe runs whole chains per launch (dn_pipe_set_group(p, 0) first)");
     if (depth == p->depth) return DN_OK;
     // nothing may be in flight: the slots are re-laid out
@@ -1010,7 +1010,7 @@ int dn_pipe_set_group(dn_pipe* p, int32_t hops) {
     if (!p) return fail(DN_ERR_INVALID, "dn_pipe_set_group: null pipe");
     if (hops < 0 || hops > DN_PIPE_MAX_GROUP) return fail(DN_ERR_INVALID, "dn_pipe_set_group: hops must be in 0.." + std::to_string(DN_PIPE_MAX_GROUP));
     if (hops > 0 && p->d->cfg.n_fft != 1024)
-        return fail(DN_ERR_UNSUPPORTED, "hop groups run whole Griffin-Lim chains one wavefront per stream, which is built for n_fft 1024 (at 1536 that form measured slower than a wavefront per column)");
+        return fail(DN_ERR_UNSUPPORTED, "hop groups run whole Griffin-Lim chains one wavefront per stream, which is built for n_fft 1024 (at 1536 that form measured slower than a wavefront per column; at 512 it is not built)");
     if (hops > 0 && p->depth > 1) return fail(DN_ERR_INVALID, "dn_pipe_set_group: the pipe is deeper than one hop (dn_pipe_set_depth(p, 1) first)");
     if (hops > 0 && p->hio) return fail(DN_ERR_UNSUPPORTED, "dn_pipe_set_group: the host-buffer transport moves single hops");
     if (hops == p->group) return DN_OK;
@@ -1046,7 +1046,7 @@ int dn_pipe_set_gl_schedule(dn_pipe* p, int32_t schedule) {
     if (schedule != DN_GL_AUTO && schedule != DN_GL_WAVE_PER_COLUMN && schedule != DN_GL_WAVE_PER_STREAM)
         return fail(DN_ERR_INVALID, "dn_pipe_set_gl_schedule: unknown schedule");
     if (schedule == DN_GL_WAVE_PER_STREAM && p->d->cfg.n_fft != 1024)
-        return fail(DN_ERR_UNSUPPORTED, "the wavefront-per-stream Griffin-Lim is built for n_fft 1024 (at 1536 the per-lane state of a stream does not fit a wavefront's registers)");
+        return fail(DN_ERR_UNSUPPORTED, "the wavefront-per-stream Griffin-Lim is built for n_fft 1024 (at 1536 the per-lane state of a stream does not fit a wavefront's registers; at 512 the schedule is not built)");
     if (schedule == DN_GL_WAVE_PER_COLUMN && p->depth > 1)
         return fail(DN_ERR_INVALID, "a pipe deeper than one hop runs a wavefront per stream and chain segment");
     p->gl_schedule = schedule;
@@ -1057,7 +1057,7 @@ int dn_pipe_set_split(dn_pipe* p, int32_t mode) {
     if (!p) return fail(DN_ERR_INVALID, "dn_pipe_set_split: null pipe");
     if (mode != DN_SPLIT_AUTO && mode != DN_SPLIT_OFF && mode != DN_SPLIT_ON) return fail(DN_ERR_INVALID, "dn_pipe_set_split: unknown mode");
     if (mode == DN_SPLIT_ON && p->d->cfg.n_fft != 1024)
-        return fail(DN_ERR_UNSUPPORTED, "the split hop belongs to the wavefront-per-stream Griffin-Lim, which is built for n_fft 1024");
+        return fail(DN_ERR_UNSUPPORTED, "the split hop belongs to the wavefront-per-stream Griffin-Lim, which is built for n_fft 1024 (not for 512 or 1536)");
     if (mode == DN_SPLIT_ON && p->gl_split > 0)
         return fail(DN_ERR_INVALID, "dn_pipe_set_split: the pipe runs a head start (a front workgroup that goes on with its frame's chain cannot be a launch of its own): "
                                     "dn_pipe_set_head_start(p, 0) first");
@@ -1705,7 +1705,7 @@ int dn_sessions_set_schedule(dn_sessions* s, int32_t schedule) {
     if (schedule != DN_SESS_AUTO && schedule != DN_SESS_ONE_LAUNCH && schedule != DN_SESS_TWO_LAUNCHES)
         return fail(DN_ERR_INVALID, "dn_sessions_set_schedule: unknown schedule");
     if (schedule == DN_SESS_TWO_LAUNCHES && s->d->cfg.n_fft != 1024)
-        return fail(DN_ERR_UNSUPPORTED, "dn_sessions_set_schedule: the two-launch form runs a wavefront per Griffin-Lim chain, which is built for n_fft 1024");
+        return fail(DN_ERR_UNSUPPORTED, "dn_sessions_set_schedule: the two-launch form runs a wavefront per Griffin-Lim chain, which is built for n_fft 1024 (not for 512 or 1536)");
     s->schedule = schedule;
     return DN_OK;
 }

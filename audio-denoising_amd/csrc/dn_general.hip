@@ -160,6 +160,7 @@ void launch_stft_general(const DspDev& d, const float* x, float* spec, float* lo
     const int T = 1 + L / (d.n_fft / 2);
     float2* sp = reinterpret_cast<float2*>(spec);
     if (d.n_fft == 1536) hipLaunchKernelGGL(stft_general_kernel<1536>, dim3(B * T), dim3(64), 0, st, d, x, L, T, sp, logmel);
+    else if (d.n_fft == 512) hipLaunchKernelGGL(stft_general_kernel<512>, dim3(B * T), dim3(64), 0, st, d, x, L, T, sp, logmel);
     else hipLaunchKernelGGL(stft_general_kernel<1024>, dim3(B * T), dim3(64), 0, st, d, x, L, T, sp, logmel);
 }
 
@@ -168,12 +169,14 @@ void launch_server_rows(const DspDev& d, const float* logmel, const float* model
     const float2* si = reinterpret_cast<const float2*>(spec_in);
     float2* so = reinterpret_cast<float2*>(spec_out);
     if (d.n_fft == 1536) hipLaunchKernelGGL(server_rows_kernel<1536>, dim3(rows), dim3(kInvThreads), 0, st, d, logmel, model_out, si, so);
+    else if (d.n_fft == 512) hipLaunchKernelGGL(server_rows_kernel<512>, dim3(rows), dim3(kInvThreads), 0, st, d, logmel, model_out, si, so);
     else hipLaunchKernelGGL(server_rows_kernel<1024>, dim3(rows), dim3(kInvThreads), 0, st, d, logmel, model_out, si, so);
 }
 
 void launch_istft_general(const DspDev& d, const float* spec, float* wave, int B, int T, hipStream_t st) {
     const float2* sp = reinterpret_cast<const float2*>(spec);
     if (d.n_fft == 1536) hipLaunchKernelGGL(istft_general_kernel<1536>, dim3(B * (T - 1)), dim3(128), 0, st, d, sp, T, wave);
+    else if (d.n_fft == 512) hipLaunchKernelGGL(istft_general_kernel<512>, dim3(B * (T - 1)), dim3(128), 0, st, d, sp, T, wave);
     else hipLaunchKernelGGL(istft_general_kernel<1024>, dim3(B * (T - 1)), dim3(128), 0, st, d, sp, T, wave);
 }
 

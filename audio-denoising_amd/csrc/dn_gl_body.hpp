@@ -68,7 +68,9 @@ __device__ __forceinline__ v2f rand_angle_mid(uint64_t seed, uint64_t sid, int c
 // it spilled ~75 of them to scratch in every iteration (188 us per batch-256 hop, round 1).
 template <int NFFT> constexpr bool gl_lean() { return NFFT == 1536; }
 template <int NFFT> constexpr int gl_tables() { return gl_lean<NFFT>() ? 8 * (4 * Geo<NFFT>::kNC + Geo<NFFT>::Fft::kPdTable) : 0; }
-template <int NFFT> constexpr int gl_smem() { return 8 * 3 * Geo<NFFT>::kTile + 4 * 2 * 2 * NFFT + gl_tables<NFFT>(); }    // 30,208 B at 1024, 77,824 B at 1536
+// the three exchange tiles; the prologue's inverse-mel fold borrows them first and needs 8 KB, more than the tiles themselves at n_fft 512
+template <int NFFT> constexpr int gl_tiles() { return 8 * 3 * Geo<NFFT>::kTile > 16 * (kInvThirds + 1) * kMaxMels ? 8 * 3 * Geo<NFFT>::kTile : 16 * (kInvThirds + 1) * kMaxMels; }
+template <int NFFT> constexpr int gl_smem() { return gl_tiles<NFFT>() + 4 * 2 * 2 * NFFT + gl_tables<NFFT>(); }    // 16,384 B at 512, 30,208 B at 1024, 77,824 B at 1536
 
 // One workgroup (192 threads = 3 wavefronts = 3 columns) runs all iterations for stream `b`.  `smem`: gl_smem<NFFT>() bytes.
 // STREAM = true: instead of storing the frame, fold it into the stream's overlap-add line (P12, app3.py:219-224):
@@ -92,9 +94,10 @@ __device__ __forceinline__ void gl_body(char* smem, const DspDev& d, const float
     constexpr int kBinPad = (kBins + 7) & ~7;                  // row stride of the LDS magnitude scratch
     v2f (*tile)[kFftTile] = reinterpret_cast<v2f (*)[kFftTile]>(smem);
     // [ping-pong][0: centre column, 1: halves of columns 0 and 2][n]
-    float (*ybuf)[2][kNR] = reinterpret_cast<float (*)[2][kNR]>(smem + 8 * 3 * kFftTile);
+    constexpr int kTiles = gl_tiles<NFFT>();
+    float (*ybuf)[2][kNR] = reinterpret_cast<float (*)[2][kNR]>(smem + kTiles);
     constexpr bool kLean = gl_lean<NFFT>();
-    v2f* wsyn_t = reinterpret_cast<v2f*>(smem + 8 * 3 * kFftTile + 4 * 2 * 2 * kNR);        // [NC]       lean only
+    v2f* wsyn_t = reinterpret_cast<v2f*>(smem + kTiles + 4 * 2 * 2 * kNR);        // [NC]       lean only
     v2f* cw_t = wsyn_t + kNC;                                                                // [3][NC]
     v2f* pd_t = kLean ? cw_t + 3 * kNC : nullptr;                                            // [11][64]
 
@@ -128,7 +131,7 @@ __device__ __forceinline__ void gl_body(char* smem, const DspDev& d, const float
             // factored form, in the canonical order of dn_invmel_body.hpp (the FFT tiles are free until the first iteration)
             float4* yp4 = reinterpret_cast<float4*>(smem);
             float4* y4 = yp4 + kInvThirds * kMaxMels;
-            static_assert(16 * (kInvThirds + 1) * kMaxMels <= 8 * 3 * kFftTile && 16 * kInvMel4 <= 4 * 2 * kNR, "the fold's scratch fits");
+            static_assert(16 * (kInvThirds + 1) * kMaxMels <= kTiles && 16 * kInvMel4 <= 4 * 2 * kNR, "the fold's scratch fits");
             InvBandFold<kGlThreads> inv;
             inv.fetch(d, tid);
             inv.fold(d, mel4, yp4, y4, tid);

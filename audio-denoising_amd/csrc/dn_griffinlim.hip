@@ -34,6 +34,8 @@ void launch_griffinlim(const DspDev& d, const float* mag, const float* init, uin
     const v2f* ia = reinterpret_cast<const v2f*>(init);
     if (d.n_fft == 1536)
         hipLaunchKernelGGL((griffinlim_kernel<1536, false>), dim3(B), dim3(kGlThreads), 0, st, d, mag, (const float*)nullptr, ia, seed, sid0, scale, wave, n_iter, mom);
+    else if (d.n_fft == 512)
+        hipLaunchKernelGGL((griffinlim_kernel<512, false>), dim3(B), dim3(kGlThreads), 0, st, d, mag, (const float*)nullptr, ia, seed, sid0, scale, wave, n_iter, mom);
     else
         hipLaunchKernelGGL((griffinlim_kernel<1024, false>), dim3(B), dim3(kGlThreads), 0, st, d, mag, (const float*)nullptr, ia, seed, sid0, scale, wave, n_iter, mom);
 }
@@ -63,6 +65,8 @@ void launch_synthesis(const DspDev& d, const float* x, const float* diff, const 
     const v2f* ia = reinterpret_cast<const v2f*>(init);
     if (d.n_fft == 1536)
         hipLaunchKernelGGL((griffinlim_kernel<1536, true>), dim3(B), dim3(kGlThreads), 0, st, d, x, diff, ia, seed, sid0, scale, wave, n_iter, mom);
+    else if (d.n_fft == 512)
+        hipLaunchKernelGGL((griffinlim_kernel<512, true>), dim3(B), dim3(kGlThreads), 0, st, d, x, diff, ia, seed, sid0, scale, wave, n_iter, mom);
     else
         hipLaunchKernelGGL((griffinlim_kernel<1024, true>), dim3(B), dim3(kGlThreads), 0, st, d, x, diff, ia, seed, sid0, scale, wave, n_iter, mom);
 }

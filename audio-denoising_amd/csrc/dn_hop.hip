@@ -19,15 +19,19 @@
 //   advances, so one captured launch replays indefinitely under hipGraph (BASELINE config 5).
 #include "dn_hop_common.hpp"
 
-// The kernels below are instantiated in THREE translation units, because LLVM's GCN scheduling strategies suit them differently (Makefile; measured,
+// The kernels below are instantiated in FOUR translation units, because LLVM's GCN scheduling strategies suit them differently (Makefile; measured,
 // profiles/r04_group_sweep.txt):
 //   dn_hop.hip      (this file)  n_fft 1024, a wavefront per STFT column (the one-hop pipe, the unpipelined hop): max-ILP, +2..3 %;
 //   dn_hop_glw.hip  (DN_HOP_TU_GLW)   n_fft 1024, a wavefront per stream (deep pipes, the saturated regime, the front-only launch of a split hop):
 //                                     iterative-ILP, +3..7 % (1,024 streams 6.73 -> 7.00 M frames/s, the captured streaming step 6.34 -> 6.79 M);
-//   dn_hop1536.hip  (DN_HOP_TU_1536)  n_fft 1536: the default strategy (max-ILP costs it 12 %: it sits at the 256-register cap and spills more).
+//   dn_hop1536.hip  (DN_HOP_TU_1536)  n_fft 1536: the default strategy (max-ILP costs it 12 %: it sits at the 256-register cap and spills more);
+//   dn_hop512.hip   (DN_HOP_TU_512)   n_fft 512, a wavefront per STFT column: the default strategy (no strategy has been measured against it yet).
 // The stamped diagnostic build keeps everything in this file (its probe arrays are per translation unit).
 #if !defined(DN_PROBE)
 #define DN_HOP_SPLIT_TUS 1
+#endif
+#if defined(DN_HOP_TU_1536) || defined(DN_HOP_TU_512) || defined(DN_HOP_TU_GLW)
+#define DN_HOP_TU_SIDE 1          // a side unit: the kernels of one size or schedule and their launchers, nothing else
 #endif
 
 namespace dn {
@@ -50,7 +54,7 @@ static __device__ unsigned int g_hop_blk_hw[2048];          // where every workg
 #define DN_HSTAMP(id) do { } while (0)
 #endif
 
-// CT: the number of compressed mel bins when the plan has the usual one (80 mels at n_fft 1024, 64 at 1536), 0 = any (run-time lengths in the model)
+// CT: the number of compressed mel bins when the plan has the usual one (80 mels at n_fft 1024, 64 at 512 and 1536), 0 = any (run-time lengths in the model)
 // GLW: the pending hops' Griffin-Lim runs one wavefront per stream and chain segment (dn_glw_body.hpp) instead of one wavefront per column (one
 //      stream a workgroup, one pending hop).  A workgroup then holds a.spb streams x a.depth chain segments (spb x depth <= 4):
 //        depth 1  four streams a workgroup: the saturated regime (several streams per CU);
@@ -310,7 +314,7 @@ __global__ __launch_bounds__(kHopPipeThreads, FRONT ? kFrontPerCu : (NFFT == 153
 template <int NFFT, bool STREAM, bool GLW>
 static void launch_hop_n(const DspDev& d, const CellDev& c, const HopArgs& a, bool bf16, hipStream_t st) {
     const dim3 block(kHopPipeThreads);
-    constexpr int kUsualC = NFFT == 1536 ? 4 : 5;
+    constexpr int kUsualC = NFFT == 1024 ? 5 : 4;
     if constexpr (GLW) {
         if (a.front_only) {             // the second launch of a split hop: front workgroups alone, under their own register budget
             const dim3 fgrid(a.front_B);
@@ -334,7 +338,7 @@ static void launch_hop_n(const DspDev& d, const CellDev& c, const HopArgs& a, bo
     }
 }
 
-#if !defined(DN_HOP_TU_1536) && !defined(DN_HOP_TU_GLW)
+#if !defined(DN_HOP_TU_SIDE)
 // a.glw: the caller laid the grid out for a wavefront per stream and chain segment (n_fft 1024 only) instead of a wavefront per column
 // The deferred host output of the LAST push (no further launch will carry it): copy, then publish (dn_pipe_stream_host_wait).
 __global__ void host_copy_kernel(const uint4* __restrict__ src, uint4* __restrict__ dst, unsigned int n16) {
@@ -351,8 +355,10 @@ void launch_host_copy(const uint4* src, uint4* dst, unsigned int n16, unsigned l
 }
 
 void launch_hop_1536(const DspDev& d, const CellDev& c, const HopArgs& a, bool bf16, hipStream_t st);          // (dn_hop1536.hip)
+void launch_hop_512(const DspDev& d, const CellDev& c, const HopArgs& a, bool bf16, hipStream_t st);           // (dn_hop512.hip)
 void launch_hop_glw(const DspDev& d, const CellDev& c, const HopArgs& a, bool bf16, hipStream_t st);           // (dn_hop_glw.hip)
 void launch_frame_1536(const DspDev& d, const CellDev& c, const FrameArgs& a, int B, bool bf16, hipStream_t st);
+void launch_frame_512(const DspDev& d, const CellDev& c, const FrameArgs& a, int B, bool bf16, hipStream_t st);
 
 void launch_hop(const DspDev& d, const CellDev& c, const HopArgs& a, bool bf16, hipStream_t st) {
     const bool stream = a.ola != nullptr;
@@ -366,7 +372,14 @@ void launch_hop(const DspDev& d, const CellDev& c, const HopArgs& a, bool bf16, 
         launch_hop(d, c, fronts, bf16, st);
         return;
     }
-    if (d.n_fft == 1536) {
+    if (d.n_fft == 512) {          // (a wavefront per column only: dn_api.hip never asks for another schedule at this size)
+#ifdef DN_HOP_SPLIT_TUS
+        launch_hop_512(d, c, a, bf16, st);
+#else
+        if (stream) launch_hop_n<512, true, false>(d, c, a, bf16, st);
+        else launch_hop_n<512, false, false>(d, c, a, bf16, st);
+#endif
+    } else if (d.n_fft == 1536) {
 #ifdef DN_HOP_SPLIT_TUS
         launch_hop_1536(d, c, a, bf16, st);
 #else
@@ -423,7 +436,7 @@ __global__ __launch_bounds__(kHopPipeThreads, NFFT == 1536 ? 2 : 1) void frame_k
 
 template <int NFFT, bool STREAM>
 static void launch_frame_n(const DspDev& d, const CellDev& c, const FrameArgs& a, int B, bool bf16, hipStream_t st) {
-    constexpr int kUsualC = NFFT == 1536 ? 4 : 5;
+    constexpr int kUsualC = NFFT == 1024 ? 5 : 4;
     if (a.C == kUsualC) {
         if (bf16) hipLaunchKernelGGL((frame_kernel<NFFT, STREAM, true, kUsualC>), dim3(B), dim3(kHopPipeThreads), 0, st, d, c, a);
         else hipLaunchKernelGGL((frame_kernel<NFFT, STREAM, false, kUsualC>), dim3(B), dim3(kHopPipeThreads), 0, st, d, c, a);
@@ -433,10 +446,17 @@ static void launch_frame_n(const DspDev& d, const CellDev& c, const FrameArgs& a
     }
 }
 
-#if !defined(DN_HOP_TU_1536) && !defined(DN_HOP_TU_GLW)
+#if !defined(DN_HOP_TU_SIDE)
 void launch_frame(const DspDev& d, const CellDev& c, const FrameArgs& a, int B, bool bf16, hipStream_t st) {
     const bool stream = a.ring != nullptr;
-    if (d.n_fft == 1536) {
+    if (d.n_fft == 512) {
+#ifdef DN_HOP_SPLIT_TUS
+        launch_frame_512(d, c, a, B, bf16, st);
+#else
+        if (stream) launch_frame_n<512, true>(d, c, a, B, bf16, st);
+        else launch_frame_n<512, false>(d, c, a, B, bf16, st);
+#endif
+    } else if (d.n_fft == 1536) {
 #ifdef DN_HOP_SPLIT_TUS
         launch_frame_1536(d, c, a, B, bf16, st);
 #else
@@ -453,6 +473,15 @@ void launch_hop_glw(const DspDev& d, const CellDev& c, const HopArgs& a, bool bf
     if (a.ola != nullptr) launch_hop_n<1024, true, true>(d, c, a, bf16, st);
     else launch_hop_n<1024, false, true>(d, c, a, bf16, st);
 }
+#elif defined(DN_HOP_TU_512)          // the n_fft-512 translation unit
+void launch_hop_512(const DspDev& d, const CellDev& c, const HopArgs& a, bool bf16, hipStream_t st) {
+    if (a.ola != nullptr) launch_hop_n<512, true, false>(d, c, a, bf16, st);
+    else launch_hop_n<512, false, false>(d, c, a, bf16, st);
+}
+void launch_frame_512(const DspDev& d, const CellDev& c, const FrameArgs& a, int B, bool bf16, hipStream_t st) {
+    if (a.ring != nullptr) launch_frame_n<512, true>(d, c, a, B, bf16, st);
+    else launch_frame_n<512, false>(d, c, a, B, bf16, st);
+}
 #else          // the n_fft-1536 translation unit
 void launch_hop_1536(const DspDev& d, const CellDev& c, const HopArgs& a, bool bf16, hipStream_t st) {
     if (a.ola != nullptr) launch_hop_n<1536, true, false>(d, c, a, bf16, st);
@@ -466,7 +495,7 @@ void launch_frame_1536(const DspDev& d, const CellDev& c, const FrameArgs& a, in
 
 }  // namespace dn
 
-#if defined(DN_PROBE) && !defined(DN_HOP_TU_1536) && !defined(DN_HOP_TU_GLW)
+#if defined(DN_PROBE) && !defined(DN_HOP_TU_SIDE)
 // diagnostic build only: the stamps of the Griffin-Lim workgroup 0 of hop_kernel / frame_kernel
 extern "C" int dn_probe_read_hop(unsigned long long* host48) {
     return (int)hipMemcpyFromSymbol(host48, HIP_SYMBOL(dn::g_gl_probe), sizeof(dn::g_gl_probe));

@@ -32,6 +32,7 @@ static void launch_invmel_n(const DspDev& d, const float* x, const float* diff, 
 
 void launch_invmel(const DspDev& d, const float* x, const float* diff, float* lin, int rows, hipStream_t st) {
     if (d.n_fft == 1536) launch_invmel_n<1536>(d, x, diff, lin, rows, st);
+    else if (d.n_fft == 512) launch_invmel_n<512>(d, x, diff, lin, rows, st);
     else launch_invmel_n<1024>(d, x, diff, lin, rows, st);
 }
 

@@ -7,7 +7,7 @@ namespace dn {
 
 // STFT / mel / inverse-mel / Griffin-Lim constants, all resident in HBM (L2-hot: ~0.4 MB total).
 struct DspDev {
-    int n_fft;              // 1024 or 1536; NC = n_fft/2 is the complex FFT length, K = NC + 1 bins
+    int n_fft;              // 512, 1024 or 1536; NC = n_fft/2 is the complex FFT length, K = NC + 1 bins
     const float2* twc;      // [NC]     exp(-2 pi i k / NC)
     const float2* twr;      // [NC/2+1] exp(-2 pi i k / n_fft)
     const float* window;    // [n_fft]  analysis == synthesis window (periodic Hann by default)

@@ -5,7 +5,7 @@
 // gl_body and glw_body run unchanged: a session's samples are the bits dn_stream_step gives it at B = 1.
 //
 // Two schedules:
-//   sess_frame_kernel   ONE launch, one workgroup per listed slot, P1-P12 back to back (frame_kernel's form; n_fft 1024 and 1536);
+//   sess_frame_kernel   ONE launch, one workgroup per listed slot, P1-P12 back to back (frame_kernel's form; every built n_fft);
 //   sess_front_kernel + sess_chain_kernel
 //                       TWO launches (n_fft 1024): the front halves (P1-P10, stft -> GRUUNet2 -> inverse mel into a workspace row), then the
 //                       Griffin-Lim chains a wavefront per session, four a workgroup, with the overlap-add and emit epilogue (the split hop of
@@ -16,9 +16,10 @@
 // into records and sess_import_kernel scatters records into slots, a workgroup a record; sess_check_kernel validates the headers of an
 // import before anything is written.
 //
-// Three translation units, as dn_hop.hip (Makefile: the scheduling strategy of each kernel family):
+// Four translation units, as dn_hop.hip (Makefile: the scheduling strategy of each kernel family):
 //   dn_sessions.hip       (this file)            n_fft 1024 one-launch form (max-ILP, as frame_kernel), the open and record kernels, the dispatch;
 //   dn_sessions1536.hip   (DN_SESS_TU_1536)      n_fft 1536 one-launch form (default strategy);
+//   dn_sessions512.hip    (DN_SESS_TU_512)       n_fft 512 one-launch form (default strategy);
 //   dn_sessions_glw.hip   (DN_SESS_TU_GLW)       the two-launch form (iterative-ILP, as the wavefront-per-stream hop kernels).
 #include "dn_hop_common.hpp"
 
@@ -77,7 +78,7 @@ __global__ __launch_bounds__(kHopPipeThreads, NFFT == 1536 ? 2 : 1) void sess_fr
 
 template <int NFFT>
 static void launch_sess_frame_n(const DspDev& d, const CellDev& c, const SessArgs& a, bool bf16, hipStream_t st) {
-    constexpr int kUsualC = NFFT == 1536 ? 4 : 5;
+    constexpr int kUsualC = NFFT == 1024 ? 5 : 4;
     const dim3 grid(a.n), block(kHopPipeThreads);
     if (a.C == kUsualC) {
         if (bf16) hipLaunchKernelGGL((sess_frame_kernel<NFFT, true, kUsualC>), grid, block, 0, st, d, c, a);
@@ -163,11 +164,17 @@ void launch_sess_split(const DspDev& d, const CellDev& c, const SessArgs& a, boo
 void launch_sess_frame_1536(const DspDev& d, const CellDev& c, const SessArgs& a, bool bf16, hipStream_t st) {
     launch_sess_frame_n<1536>(d, c, a, bf16, st);
 }
+#elif defined(DN_SESS_TU_512)
+void launch_sess_frame_512(const DspDev& d, const CellDev& c, const SessArgs& a, bool bf16, hipStream_t st) {
+    launch_sess_frame_n<512>(d, c, a, bf16, st);
+}
 #else
 void launch_sess_frame_1536(const DspDev& d, const CellDev& c, const SessArgs& a, bool bf16, hipStream_t st);     // (dn_sessions1536.hip)
+void launch_sess_frame_512(const DspDev& d, const CellDev& c, const SessArgs& a, bool bf16, hipStream_t st);      // (dn_sessions512.hip)
 
 void launch_sess_frame(const DspDev& d, const CellDev& c, const SessArgs& a, bool bf16, hipStream_t st) {
     if (d.n_fft == 1536) launch_sess_frame_1536(d, c, a, bf16, st);
+    else if (d.n_fft == 512) launch_sess_frame_512(d, c, a, bf16, st);
     else launch_sess_frame_n<1024>(d, c, a, bf16, st);
 }
 

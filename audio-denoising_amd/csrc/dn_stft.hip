@@ -49,6 +49,7 @@ static void launch_stft_n(const DspDev& d, const float* frames, float* spec, flo
 void launch_stft(const DspDev& d, const float* frames, float* spec, float* mel, float* peak, int B, uint32_t flags,
                  hipStream_t st) {
     if (d.n_fft == 1536) launch_stft_n<1536>(d, frames, spec, mel, peak, B, flags, st);
+    else if (d.n_fft == 512) launch_stft_n<512>(d, frames, spec, mel, peak, B, flags, st);
     else launch_stft_n<1024>(d, frames, spec, mel, peak, B, flags, st);
 }
 

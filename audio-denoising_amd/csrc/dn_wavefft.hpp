@@ -3,6 +3,7 @@
 // A real transform of length n_fft is done as a complex FFT of length NC = n_fft/2 plus a
 // Hermitian split.  ONE 64-lane wavefront owns one transform and holds NV = NC/64 complex values
 // per lane; every Stockham pass is a whole number of radix-R butterflies per lane:
+//     n_fft  512: NC = 256 = 4 * 4 * 4 * 4  (NV =  4; four radix-4 passes, one butterfly per lane)
 //     n_fft 1024: NC = 512 = 8 * 8 * 8      (NV =  8; three radix-8 passes, one butterfly per lane)
 //     n_fft 1536: NC = 768 = 4 * 4 * 4 * 12 (NV = 12; three radix-4 passes of three butterflies per
 //                                             lane, then one radix-12 pass)           [app3.py:29-33]
@@ -92,6 +93,73 @@ template <bool INV> __device__ __forceinline__ v2f twmul(v2f a, v2f w) { return 
 
 // ---- per complex length: geometry, per-lane twiddles, the FFT itself -------------------------------
 template <int NC> struct WaveFft;
+
+template <> struct WaveFft<256> {
+    static constexpr int kNV = 4;
+    static constexpr int kTile = 256;        // complex entries of the exchange tile: the maps below permute it in place, no padding
+    struct Tw { v2f pb[3], pc[3], pd[3]; };  // passes B (Ns=4), C (Ns=16), D (Ns=64): r = 1..3
+    static constexpr int kPdTable = 0;
+    static __device__ __forceinline__ void fill_pd(v2f*, const v2f* __restrict__, int) {}
+    template <bool WITH_PD = true>
+    static __device__ __forceinline__ void load(Tw& tw, const v2f* __restrict__ twc, int lane) {
+#pragma unroll
+        for (int r = 1; r < 4; ++r) {
+            tw.pb[r - 1] = twc[(lane & 3) * r * 16];          // exp(-2 pi i (j%4) r / 16)
+            tw.pc[r - 1] = twc[(lane & 15) * r * 4];          // exp(-2 pi i (j%16) r / 64)
+            tw.pd[r - 1] = twc[lane * r];                     // exp(-2 pi i j r / 256)
+        }
+    }
+    // Tile index maps of the first two exchanges: XOR swizzles instead of padding.  Entry c = (c7 .. c0) is kept at c with two of its low bits
+    // flipped by (c5, c4).  What has to hold (8-byte entries; MI355X LDS):
+    //   ds_read_b64   conflicts within a half of the wave, bank pair = entry % 32.  A half reads c = lane + 64 t, lane = 0..31 or 32..63: c5 and up
+    //                 are fixed and (c4 .. c0) -> the low five bits of either map is a bijection (a bit is kept, flipped by the fixed c5, or
+    //                 XORed with c4, which is itself kept).  Conflict free.
+    //   ds_write_b64  conflicts within 16 consecutive lanes, bank pair = entry % 16.
+    //       exchange A writes c = 4 j + r: the sixteen lanes of a group differ in (c5 .. c2) and mapA's low four bits are (c3, c2, c1 ^ c5, c0 ^ c4):
+    //                 a bijection of them for the fixed r = (c1, c0) -- unswizzled, lanes j and j + 4 share a bank (four-way).
+    //       exchange B writes c = 16 (j>>2) + (j&3) + 4 r: the lanes differ in (c5, c4, c1, c0) and mapB's low four bits are (c3 ^ c5, c2 ^ c4, c1, c0):
+    //                 a bijection again for the fixed r = (c3, c2) -- unswizzled, lanes j and j + 4 share a bank.
+    //       exchange C writes c = 64 (j>>4) + (j&15) + 16 r: the lanes of a group are sixteen consecutive entries.  Conflict free as it is.
+    // On the reading side the flip depends on the lane alone (c5, c4 = lane bits 5, 4), so the four reads are one address and constant offsets.
+    static __device__ __forceinline__ int mapA(int c) { return c ^ ((c >> 4) & 3); }
+    static __device__ __forceinline__ int mapB(int c) { return c ^ (((c >> 4) & 3) << 2); }
+
+    template <bool INV>
+    static __device__ __forceinline__ void run(v2f (&v)[4], const Tw& tw, v2f* tile, int lane, const v2f* = nullptr) {
+        // pass A (Ns = 1): out[4 j + r], j = lane
+        dft4<INV>(v[0], v[1], v[2], v[3]);
+        wave_sync();                                          // previous readers of the tile are done
+#pragma unroll
+        for (int r = 0; r < 4; ++r) tile[mapA(4 * lane + r)] = v[r];
+        wave_sync();
+#pragma unroll
+        for (int t = 0; t < 4; ++t) v[t] = tile[mapA(lane + 64 * t)];
+        // pass B (Ns = 4): out[16 (j>>2) + (j&3) + 4 r]
+#pragma unroll
+        for (int r = 1; r < 4; ++r) v[r] = twmul<INV>(v[r], tw.pb[r - 1]);
+        dft4<INV>(v[0], v[1], v[2], v[3]);
+        wave_sync();
+#pragma unroll
+        for (int r = 0; r < 4; ++r) tile[mapB(16 * (lane >> 2) + (lane & 3) + 4 * r)] = v[r];
+        wave_sync();
+#pragma unroll
+        for (int t = 0; t < 4; ++t) v[t] = tile[mapB(lane + 64 * t)];
+        // pass C (Ns = 16): out[64 (j>>4) + (j&15) + 16 r]
+#pragma unroll
+        for (int r = 1; r < 4; ++r) v[r] = twmul<INV>(v[r], tw.pc[r - 1]);
+        dft4<INV>(v[0], v[1], v[2], v[3]);
+        wave_sync();
+#pragma unroll
+        for (int r = 0; r < 4; ++r) tile[64 * (lane >> 4) + (lane & 15) + 16 * r] = v[r];
+        wave_sync();
+#pragma unroll
+        for (int t = 0; t < 4; ++t) v[t] = tile[lane + 64 * t];
+        // pass D (Ns = 64): output index lane + 64 r stays in registers
+#pragma unroll
+        for (int r = 1; r < 4; ++r) v[r] = twmul<INV>(v[r], tw.pd[r - 1]);
+        dft4<INV>(v[0], v[1], v[2], v[3]);
+    }
+};
 
 template <> struct WaveFft<512> {
     static constexpr int kNV = 8;

@@ -208,7 +208,7 @@ class _Pipe:
         self.lib.check(self.lib.dn_pipe_set_gl_schedule(self.handle, int(schedule)))
 
     def set_depth(self, depth: int) -> None:
-        """dn_pipe_set_depth: hops of ONE stream in flight (1 .. 4, n_fft 1024).  With depth D a frame's Griffin-Lim chain runs as D segments
+        """dn_pipe_set_depth: hops of ONE stream in flight (1 .. 4; more than 1 at n_fft 1024 only).  With depth D a frame's Griffin-Lim chain runs as D segments
         in the D launches after its submit (bit-identical results): about one stream per CU then reaches the throughput of the saturated
         regime, for D - 1 more hops of latency.  Call while nothing is in flight."""
         with torch.cuda.device(self.dn.device):
@@ -657,7 +657,7 @@ def throughput_plan(batch: int, n_fft: int = 1024) -> dict:
       1,024 .. 2,047       two pipes on two HIP streams, split hops, two hops in flight (1,024 streams: 8.0 M frames/s against 6.9 M)
       2,048 and up         an even number of pipes of about 1,024 streams, taking turns on two HIP streams, split hops, one hop in flight
                            (2,048 / 4,096 / 8,192 streams: 8.4 M frames/s against 7.2 / 7.4 / 7.7 M for one pipe)
-    n_fft 1536 (the wavefront-per-stream schedule is not built there): one pipe at depth 1."""
+    n_fft 512 and 1536 (the wavefront-per-stream schedule is not built there): one pipe at depth 1."""
     if n_fft != 1024:
         return {"queues": 1, "pipes": 1, "depth": 1, "split": False, "group": 0}
     if batch <= 384:

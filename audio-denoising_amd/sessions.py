@@ -203,7 +203,7 @@ class SessionPool:
         self._queue.pop(int(slot), None)
 
     def set_schedule(self, schedule: int) -> None:
-        """``_lib.DN_SESS_AUTO`` / ``DN_SESS_ONE_LAUNCH`` / ``DN_SESS_TWO_LAUNCHES`` (n_fft 1024): same samples, bit for bit."""
+        """``_lib.DN_SESS_AUTO`` / ``DN_SESS_ONE_LAUNCH`` / ``DN_SESS_TWO_LAUNCHES`` (n_fft 1024 only; refused at 512 and 1536): same samples, bit for bit."""
         self.lib.check(self.lib.dn_sessions_set_schedule(self.handle, int(schedule)))
         self._schedule = int(schedule)
 

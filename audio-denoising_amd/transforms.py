@@ -24,7 +24,7 @@ from torch import nn
 
 from . import _lib
 
-_N_FFTS = (1024, 1536)   # the one-wave FFT kernels: 512 = 8*8*8 and 768 = 4*4*4*12 complex points (hop = n_fft/2)
+_N_FFTS = (512, 1024, 1536)   # the one-wave FFT kernels: 256 = 4*4*4*4, 512 = 8*8*8 and 768 = 4*4*4*12 complex points (hop = n_fft/2)
 
 
 def melscale_fbanks(n_freqs: int, f_min: float, f_max: float, n_mels: int, sample_rate: int) -> torch.Tensor:

@@ -134,7 +134,8 @@ int dn_momo_forward(const dn_momo* m, const float* x, const float* hx_in, const 
 
 typedef struct dn_dsp_cfg {
     int32_t sample_rate;
-    int32_t n_fft;   /* 1024 (hop = n_fft/2, win_length = n_fft) */
+    int32_t n_fft;   /* 512, 1024 or 1536 (hop = n_fft/2, win_length = n_fft); any other size: DN_ERR_UNSUPPORTED.  512 runs the one-hop
+                      * schedules only (unpipelined hop, pipe of depth 1, one-launch sessions, the general kernels): see the setters below */
     int32_t hop;
     int32_t n_mels;  /* 0 = no mel stages */
 } dn_dsp_cfg;
@@ -262,9 +263,9 @@ int dn_pipe_set_model(dn_pipe* p, const dn_model* m);
 /* Head start: a front workgroup is done with P1-P10 well before the pending hop's Griffin-Lim chain (same launch) is; with
  * `iterations` > 0 it goes on with the first iterations of ITS frame's chain and parks it in HBM, and the next launch resumes there.
  * Same results bit for bit, no added latency; pays when there is about one stream per CU.  dn_pipe_create turns it on by itself up to
- * 256 streams (8 iterations at n_fft 1024, 12 at 1536: the measured optima).  Call between launches (0 = off). */
+ * 256 streams (8 iterations at n_fft 1024, 12 at 1536: the measured optima; 512 takes 1024's).  Call between launches (0 = off). */
 int dn_pipe_set_head_start(dn_pipe* p, int32_t iterations);
-/* Depth of the pipe = hops of ONE stream in flight (n_fft 1024; DN_ERR_UNSUPPORTED at 1536, where the per-lane state of a stream does not fit one wavefront).  1 (default): hop n's Griffin-Lim runs beside hop n+1's front half, as
+/* Depth of the pipe = hops of ONE stream in flight (n_fft 1024; DN_ERR_UNSUPPORTED at 1536, where the per-lane state of a stream does not fit one wavefront, and at 512, where the schedule is not built).  1 (default): hop n's Griffin-Lim runs beside hop n+1's front half, as
  * described above.  D > 1: a frame's Griffin-Lim chain is cut into D segments that run in the D launches after its submit -- one wavefront
  * per stream and segment (DN_GL_WAVE_PER_STREAM), the chain parked in HBM between launches at the top of an iteration, so the result is
  * bit-identical to depth 1 -- and a launch carries the segments of D different hops of every stream.  With about one stream per CU (the
@@ -274,7 +275,7 @@ int dn_pipe_set_head_start(dn_pipe* p, int32_t iterations);
  * Call while nothing is in flight (after create or flush); synchronises the device. */
 #define DN_PIPE_MAX_DEPTH 4
 int dn_pipe_set_depth(dn_pipe* p, int32_t depth);
-/* Hop groups (n_fft 1024; DN_ERR_UNSUPPORTED at 1536, where the form measured slower than the one-hop pipe): the loop body of app3.py:178-226 for `hops` CONSECUTIVE hops of every stream in ONE launch.
+/* Hop groups (n_fft 1024; DN_ERR_UNSUPPORTED at 1536, where the form measured slower than the one-hop pipe, and at 512, where it is not built): the loop body of app3.py:178-226 for `hops` CONSECUTIVE hops of every stream in ONE launch.
  * A deep pipe (above) pays for every launch boundary inside a Griffin-Lim chain: the chain parks in HBM and comes back at the head of the next
  * launch.  With dn_pipe_set_group(p, H), 1 <= H <= DN_PIPE_MAX_GROUP, a launch is as long as a chain instead: dn_pipe_submit_group carries up to H
  * new hops of every stream -- hop h of the group reads frames + h * frames_stride, its front half (P1-P10) runs behind hop h-1's with hx handed on,
@@ -298,7 +299,8 @@ int dn_pipe_stream_push_group(dn_pipe* p, const void* hop_in, int64_t in_stride,
                               int32_t out_is_s16, const float* init_angles, int64_t init_stride, uint64_t seed, uint64_t stream_id0,
                               int32_t n_iter, float momentum, void* stream);
 int dn_pipe_stream_flush_group(dn_pipe* p, void* hop_out, int64_t out_stride, int32_t out_is_s16, int32_t* hops_valid, void* stream);
-/* How the pending hop's Griffin-Lim is laid out on the GPU (n_fft 1024; results are bit-identical either way):
+/* How the pending hop's Griffin-Lim is laid out on the GPU (n_fft 1024; results are bit-identical either way; at 512 and 1536 only the
+ * per-column form exists: DN_GL_AUTO resolves to it and DN_GL_WAVE_PER_STREAM is DN_ERR_UNSUPPORTED):
  *   DN_GL_WAVE_PER_COLUMN  three wavefronts per stream, one per STFT column: the shortest chain for one stream -- right when there is
  *                          about one stream per CU (the batch-256 metric);
  *   DN_GL_WAVE_PER_STREAM  one wavefront per stream, the three columns interleaved inside it, four streams per workgroup: no workgroup
@@ -312,7 +314,7 @@ int dn_pipe_set_gl_schedule(dn_pipe* p, int32_t schedule);
 /* A hop as TWO launches instead of one: first the Griffin-Lim chains of the hops in flight (what a flush launch is), then the new hop's front
  * halves (P1-P10) as a launch of their own.  Where a launch carries several times the workgroups the GPU holds at once its chains and its front
  * halves run as two phases anyway, and a front workgroup compiled into the same kernel as a chain inherits the chain's register budget (two
- * workgroups per CU); on their own four fit.  Only with the wavefront-per-stream schedule (n_fft 1024) and no head start; same control block,
+ * workgroups per CU); on their own four fit.  Only with the wavefront-per-stream schedule (n_fft 1024; DN_SPLIT_ON is DN_ERR_UNSUPPORTED at 512 and 1536) and no head start; same control block,
  * same samples, still capturable (two kernel nodes).  DN_SPLIT_AUTO (default) decides from the number of chain wavefronts per launch. */
 #define DN_SPLIT_AUTO (-1)
 #define DN_SPLIT_OFF 0
@@ -401,9 +403,9 @@ int dn_pipe_stream_set_state(dn_pipe* p, const float* ring, const float* ola, co
  * NOT thread-safe (one host thread at a time per pool) and NOT capturable into a hipGraph (the list changes every tick).
  *
  * Schedules (dn_sessions_set_schedule):
- *   DN_SESS_ONE_LAUNCH    one workgroup per listed slot runs P1-P12 back to back (n_fft 1024 and 1536);
+ *   DN_SESS_ONE_LAUNCH    one workgroup per listed slot runs P1-P12 back to back (n_fft 512, 1024 and 1536);
  *   DN_SESS_TWO_LAUNCHES  the front halves (P1-P10) of all listed slots, then their Griffin-Lim chains a wavefront per
- *                         session (n_fft 1024); the same samples, bit for bit;
+ *                         session (n_fft 1024; DN_ERR_UNSUPPORTED at 512 and 1536); the same samples, bit for bit;
  *   DN_SESS_AUTO          (default) two launches from 1,024 listed slots on at n_fft 1024 (the measured crossover: DESIGN.md 4.11).
  * flags of dn_sessions_create: DN_CONV_BF16 or 0.  The pool holds a reference on its model and plan (as a dn_pipe). */
 typedef struct dn_sessions dn_sessions;
@@ -433,7 +435,7 @@ int dn_sessions_get_counters(dn_sessions* s, int32_t id, uint64_t* frames, int32
  *   R_o  ola  [n_fft]   float32  R_o = 64 + A(4 n_fft)      the overlap-add line (app3.py:133)
  *   H_o  hx   [17][C]   float32  H_o = R_o + A(4 n_fft)     the GRU hidden state
  *   stride = dn_sessions_record_bytes = round_up(H_o + 4 * 17 * C, 256);  A(x) = round_up(x, 16); the rest is zero.
- * n_fft 1024 / 80 mels: 8,704 B a record.  A list of n records is [n][stride], record i at i * stride, in device memory
+ * n_fft 1024 / 80 mels: 8,704 B a record; n_fft 512 / 64 mels: 4,608 B.  A list of n records is [n][stride], record i at i * stride, in device memory
  * aligned to 16 bytes (else DN_ERR_INVALID).
  * The header's counters are the slot's: `pushes` counts its pushes up to n_fft/hop - 1 (primed when equal), `frames`
  * the frames run since its open (frame f draws its phases from (seed + f, stream_id)).
