@@ -24,7 +24,7 @@ class Denoiser:
     """Batched, fused hop pipeline bound to one model and one DSP plan on one GPU."""
 
     def __init__(self, model: GRUUNet2, sample_rate: int, n_fft: int = 1024, hop_length: int = 512, n_mels: int = 80,
-                 n_iter: int = 32, momentum: float = 0.99, device=None):
+                 n_iter: int = 32, momentum: float = 0.99, device=None, window: torch.Tensor | None = None):
         self.device = torch.device(device if device is not None else next(model.parameters()).device)
         if self.device.type != "cuda":
             raise RuntimeError("Denoiser needs a 'cuda' device; there is no CPU path in this package")
@@ -38,7 +38,8 @@ class Denoiser:
         self.num_compressed_bins = n_mels // 16
         # the same construction-time tensors the reference's transforms build (app3.py:135-155)
         fb = melscale_fbanks(self.n_stft, 0.0, float(sample_rate // 2), n_mels, sample_rate)
-        self.plan = DspPlan(self.device, sample_rate, n_fft, hop_length, n_mels, fb=fb, window=torch.hann_window(n_fft))
+        # ``window`` (n_fft,): what another ``window_fn`` would return; the reference passes torch.hann_window (app3.py:155)
+        self.plan = DspPlan(self.device, sample_rate, n_fft, hop_length, n_mels, fb=fb, window=torch.hann_window(n_fft) if window is None else window)
         self._ws = None
         self._calls = 0
 
@@ -127,7 +128,7 @@ class ServerDenoiser:
     hop*(L//hop) samples (InverseSpectrogram with length=None).  Four launches; no CPU fallback."""
 
     def __init__(self, model: GRUUNet2, sample_rate: int = 48000, n_fft: int = 1024, hop_length: int = 512, n_mels: int = 64,
-                 hx_decay: float = 0.9, device=None):
+                 hx_decay: float = 0.9, device=None, window: torch.Tensor | None = None):
         self.device = torch.device(device if device is not None else next(model.parameters()).device)
         if self.device.type != "cuda":
             raise RuntimeError("ServerDenoiser needs a 'cuda' device; there is no CPU path in this package")
@@ -136,7 +137,7 @@ class ServerDenoiser:
         self.sample_rate, self.n_fft, self.hop, self.n_mels = sample_rate, n_fft, hop_length, n_mels
         self.n_stft = n_fft // 2 + 1
         fb = melscale_fbanks(self.n_stft, 0.0, float(sample_rate // 2), n_mels, sample_rate)        # server.py:175-176
-        self.plan = DspPlan(self.device, sample_rate, n_fft, hop_length, n_mels, fb=fb, window=torch.hann_window(n_fft))
+        self.plan = DspPlan(self.device, sample_rate, n_fft, hop_length, n_mels, fb=fb, window=torch.hann_window(n_fft) if window is None else window)
 
     def process(self, x: torch.Tensor, hx: torch.Tensor | None = None):
         """x (B, L) float32 on the GPU, hx (B,17,C) or None -> (wave (B, hop*(L//hop)), hx_new)."""

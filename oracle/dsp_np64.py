@@ -22,22 +22,31 @@ def reflect_pad(x: np.ndarray, p: int) -> np.ndarray:
     return np.concatenate([left, x, right], axis=1)
 
 
-def stft(x: np.ndarray, n_fft: int, hop: int) -> np.ndarray:
-    """(B, L) -> (B, K, T) complex128; centred, reflect padded, Hann, one-sided."""
+def _window(n_fft: int, window) -> np.ndarray:
+    """None -> the exact periodic Hann; else the caller's (n_fft,) window (an fp32 array as the fp32 paths hold it) in float64."""
+    if window is None:
+        return hann(n_fft)
+    w = np.asarray(window, dtype=np.float64)
+    assert w.shape == (n_fft,), w.shape
+    return w
+
+
+def stft(x: np.ndarray, n_fft: int, hop: int, window=None) -> np.ndarray:
+    """(B, L) -> (B, K, T) complex128; centred, reflect padded, windowed (None: Hann), one-sided."""
     x = np.asarray(x, dtype=np.float64)
     xp = reflect_pad(x, n_fft // 2)
     n_cols = 1 + (xp.shape[1] - n_fft) // hop
-    w = hann(n_fft)
+    w = _window(n_fft, window)
     cols = [np.fft.rfft(xp[:, t * hop:t * hop + n_fft] * w, axis=1) for t in range(n_cols)]
     return np.stack(cols, axis=2)
 
 
-def istft(spec: np.ndarray, n_fft: int, hop: int) -> np.ndarray:
-    """(B, K, T) -> (B, hop*(T-1)); irfft, window, overlap-add, divide by the
+def istft(spec: np.ndarray, n_fft: int, hop: int, window=None) -> np.ndarray:
+    """(B, K, T) -> (B, hop*(T-1)); irfft, window (None: Hann), overlap-add, divide by the
     window-square envelope, trim n_fft/2 from both ends."""
     spec = np.asarray(spec, dtype=np.complex128)
     b, _, n_cols = spec.shape
-    w = hann(n_fft)
+    w = _window(n_fft, window)
     total = n_fft + hop * (n_cols - 1)
     acc = np.zeros((b, total))
     env = np.zeros(total)
@@ -78,15 +87,15 @@ def inverse_mel_scale(mel: np.ndarray, fb: np.ndarray) -> np.ndarray:
 
 
 def griffinlim(mag: np.ndarray, n_fft: int, hop: int, init_angles: np.ndarray, n_iter: int = 32,
-               momentum: float = 0.99) -> np.ndarray:
-    """Fast Griffin-Lim with momentum/(1+momentum); init_angles (B,K,T) complex."""
+               momentum: float = 0.99, window=None) -> np.ndarray:
+    """Fast Griffin-Lim with momentum/(1+momentum); init_angles (B,K,T) complex; window None: Hann."""
     mag = np.asarray(mag, np.float64)
     ang = np.asarray(init_angles, np.complex128)
     mu = momentum / (1.0 + momentum)
     prev = np.zeros_like(ang)
     for _ in range(n_iter):
-        rebuilt = stft(istft(ang * mag, n_fft, hop), n_fft, hop)
+        rebuilt = stft(istft(ang * mag, n_fft, hop, window), n_fft, hop, window)
         ang = rebuilt - mu * prev
         ang = ang / (np.abs(ang) + 1e-16)
         prev = rebuilt
-    return istft(ang * mag, n_fft, hop)
+    return istft(ang * mag, n_fft, hop, window)

@@ -22,18 +22,26 @@ def hann(n: int, dtype=torch.float32) -> torch.Tensor:
     return torch.hann_window(n, dtype=dtype)
 
 
-def spectrogram(x: torch.Tensor, n_fft: int, hop: int) -> torch.Tensor:
+def _window(n_fft: int, dtype, window) -> torch.Tensor:
+    """None -> window_fn=torch.hann_window as the reference passes it; else the (n_fft,) tensor another window_fn would return."""
+    if window is None:
+        return hann(n_fft, dtype)
+    assert tuple(window.shape) == (n_fft,), tuple(window.shape)
+    return window.to(dtype)
+
+
+def spectrogram(x: torch.Tensor, n_fft: int, hop: int, window: torch.Tensor | None = None) -> torch.Tensor:
     """Spectrogram(power=None, center=True, pad_mode='reflect', onesided=True,
     normalized=False).  (B, L) -> (B, n_fft/2+1, 1+L/hop) complex.  app3.py:135-139,191."""
-    return torch.stft(x, n_fft, hop_length=hop, win_length=n_fft, window=hann(n_fft, x.dtype),
+    return torch.stft(x, n_fft, hop_length=hop, win_length=n_fft, window=_window(n_fft, x.dtype, window),
                       center=True, pad_mode="reflect", normalized=False, onesided=True,
                       return_complex=True)
 
 
-def inverse_spectrogram(spec: torch.Tensor, n_fft: int, hop: int) -> torch.Tensor:
+def inverse_spectrogram(spec: torch.Tensor, n_fft: int, hop: int, window: torch.Tensor | None = None) -> torch.Tensor:
     """InverseSpectrogram / torch.istft(center=True, length=None).  server.py:174,216."""
     real_dtype = torch.float64 if spec.dtype == torch.complex128 else torch.float32
-    return torch.istft(spec, n_fft, hop_length=hop, win_length=n_fft, window=hann(n_fft, real_dtype),
+    return torch.istft(spec, n_fft, hop_length=hop, win_length=n_fft, window=_window(n_fft, real_dtype, window),
                        center=True, normalized=False, onesided=True, length=None)
 
 
@@ -70,14 +78,14 @@ def inverse_mel_scale(mel: torch.Tensor, fb: torch.Tensor) -> torch.Tensor:
 
 def griffinlim(mag: torch.Tensor, n_fft: int, hop: int, n_iter: int = 32, momentum: float = 0.99,
                init_angles: torch.Tensor | None = None, power: float = 1.0,
-               generator: torch.Generator | None = None) -> torch.Tensor:
+               generator: torch.Generator | None = None, window: torch.Tensor | None = None) -> torch.Tensor:
     """GriffinLim(power=1, n_iter=32, momentum=0.99, rand_init=True, length=None).
     (B, K, T) magnitude -> (B, hop*(T-1)) waveform.  app3.py:149-153, 213.
 
     ``init_angles`` (B, K, T) complex replaces the reference's
     ``torch.rand(shape, dtype=complex64)`` draw so that runs are comparable."""
     cdtype = torch.complex128 if mag.dtype == torch.float64 else torch.complex64
-    window = hann(n_fft, mag.dtype)
+    window = _window(n_fft, mag.dtype, window)
     m = momentum / (1.0 + momentum)
     shape = mag.shape
     spec = mag.reshape(-1, shape[-2], shape[-1]).pow(1.0 / power)

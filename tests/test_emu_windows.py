@@ -1,0 +1,282 @@
+"""Caller-supplied windows on the host emulation of the kernel sources (no GPU needed): every DSP entry point that reads the window or the
+tables built from it, at n_fft 512 / 1024 / 1536, with an asymmetric nowhere-zero window and with periodic Hamming, against float64
+(oracle/dsp_np64.py, oracle/pipeline_np64.py on the fp32 window and filterbank values).  tests/dsp_cases.py says what the periodic Hann of
+every other test cannot see: sample 0 of a column (w[0] = 0), which column's envelope table is which (Hann's envelope is even), and a
+mirrored read of the window (Hann is symmetric).
+
+Bars are the project's for the same stage, imported from tests/test_gpu_parity.py: STFT 2e-6 max|ref| + 1e-6, log-mel 2e-5, round trip
+2e-5, residual / hx TOL_RESIDUAL, waveform TOL_WAVE_RMS / TOL_WAVE_MAX through _wave_close at scale max(1, RMS of the float64 waveform)
+(the signals here have RMS ~ 1).  Every stream is compared.  A failing comparison prints where the error sits (per column, per half-frame,
+sample 0).  Small shapes: the emulator runs a work-item per OS thread; the gpu tier (tests/test_gpu_windows.py) runs the batches.
+
+What these tests catch and the Hann tests do not was tried on a scratch copy with two edits, one at a time (54 emulation tests from before,
+the 33 here).  (a) dn_api.hip builds the wave-per-stream tables of columns 0 and 2 from column 1's source indices: 8 of the 54 fail -- the
+schedule bit-identities, which see column 2's two-sample envelope shift under Hann too (tests/dsp_cases.py names them) -- and 8 of the 33,
+every pipe, group and session case here.  (b) dn_gl_body.hpp drops column 0's reflection: all 54 pass, 14 of the 33 fail -- the eleven
+asymmetric-window cases that run Griffin-Lim, against float64, and three Hamming cases (pipe / depth 2, groups of 2 and 4) through the bit
+identity with the untouched host-built tables, fp32 Hamming's envelope being even only to rounding.
+"""
+import ctypes as C
+import os
+import sys
+
+import numpy as np
+import pytest
+
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "emu"))
+import emu  # noqa: E402
+import dsp_cases as dc  # noqa: E402
+from audio_denoising_amd._lib import (DN_GL_AUTO, DN_GL_WAVE_PER_COLUMN, DN_GL_WAVE_PER_STREAM, DN_PEAK_NORMALIZE, DN_PRE_WINDOW,  # noqa: E402
+                                      DN_SESS_ONE_LAUNCH, DN_SESS_TWO_LAUNCHES, DspCfg)
+from oracle import dsp_np64, pipeline_ref  # noqa: E402
+from test_emu_kernels import _run_groups, _run_pipe, make_model  # noqa: E402
+from test_emu_sessions import Pool  # noqa: E402
+from test_gpu_parity import TOL_RESIDUAL, _wave_close  # noqa: E402
+
+CASES = [(n, w) for n in dc.N_FFTS for w in dc.WINDOWS]
+IDS = [f"{n}-{w}" for n, w in CASES]
+TOL_LOGMEL = 2e-5
+TOL_ROUND_TRIP = 2e-5
+
+
+def stft_bar(ref):
+    return 2e-6 * float(np.abs(ref).max()) + 1e-6
+
+
+def geometry(n_fft):
+    sr, n_mels = dc.HOP_GEOMETRY[n_fft]
+    return pipeline_ref.Params(sr, n_fft, n_fft // 2, n_mels)
+
+
+@pytest.fixture(scope="module")
+def lib():
+    return emu.load()
+
+
+@pytest.fixture(scope="module")
+def plans(lib):
+    """(n_fft, window name) -> plan with the hop geometry's filterbank, built on first use"""
+    made = {}
+
+    def get(n_fft, name):
+        if (n_fft, name) not in made:
+            p = geometry(n_fft)
+            h = C.c_void_p()
+            lib.check(lib.dn_dsp_create(C.byref(DspCfg(p.sample_rate, p.n_fft, p.hop, p.n_mels)), emu.ptr(emu.f32(dc.fbank(p))), None,
+                                        emu.ptr(emu.f32(dc.window(name, n_fft))), C.byref(h)))
+            made[(n_fft, name)] = h
+        return made[(n_fft, name)]
+    yield get
+    for h in made.values():
+        lib.dn_dsp_destroy(h)
+
+
+@pytest.fixture(scope="module")
+def model(lib):
+    m = make_model(lib, 4)              # 64 mels = 4 compressed bins at every geometry here
+    yield m
+    lib.dn_model_destroy(m)
+
+
+def wave_close(got, ref, n_fft, what=""):
+    """_wave_close at scale max(1, RMS of the float64 waveform); a failure says where the error sits"""
+    rms, mx, scale = dc.wave_errors(got, ref)
+    try:
+        _wave_close(got, ref, scale=scale)
+    except AssertionError:
+        raise AssertionError(f"{what}: rms {rms:.2e} max {mx:.2e} (scale {scale:.2f}); {dc.error_pattern(got, ref, n_fft)}") from None
+    return rms, mx
+
+
+# ------------------------------------------------------------------ the transforms
+@pytest.mark.parametrize("n_fft,name", CASES, ids=IDS)
+def test_stft_and_istft_with_the_window(lib, plans, n_fft, name):
+    """dn_stft of noise frames and dn_istft of a NON-consistent spectrogram against float64; istft(stft(x)) == x."""
+    dsp, hop, w, B = plans(n_fft, name), n_fft // 2, dc.window(name, n_fft), 2
+    x = dc.noise((B, n_fft), 100 + n_fft)
+    spec = np.zeros((B, 3, hop + 1, 2), np.float32)
+    lib.check(lib.dn_stft(dsp, emu.ptr(x), emu.ptr(spec), B, 0, None))
+    ref = dsp_np64.stft(x, n_fft, hop, window=w)
+    assert np.abs(dc.cplx(spec) - ref).max() <= stft_bar(ref), dc.error_pattern(dc.cplx(spec), ref, n_fft)
+    back = np.zeros((B, n_fft), np.float32)
+    lib.check(lib.dn_istft(dsp, emu.ptr(spec), emu.ptr(back), B, None))
+    assert np.abs(back - x).max() <= TOL_ROUND_TRIP, dc.error_pattern(back, x, n_fft)
+    mag, ang = dc.magnitudes(B, n_fft, 200 + n_fft)
+    z = ang * mag
+    wave = np.zeros((B, n_fft), np.float32)
+    lib.check(lib.dn_istft(dsp, emu.ptr(dc.ri(z)), emu.ptr(wave), B, None))
+    wave_close(wave, dsp_np64.istft(z, n_fft, hop, window=w), n_fft, "dn_istft")
+
+
+@pytest.mark.parametrize("n_fft,name", CASES, ids=IDS)
+def test_general_length_stft_and_istft_with_the_window(lib, plans, n_fft, name):
+    """dn_stft_general / dn_istft_general (inv_env[n] per output hop): a ragged length (T = 4) and the minimum (L = hop + 1, T = 2)."""
+    dsp, hop, w, B = plans(n_fft, name), n_fft // 2, dc.window(name, n_fft), 2
+    for L in (3 * hop + 37, hop + 1):
+        T = 1 + L // hop
+        x = dc.noise((B, L), 300 + L)
+        spec = np.zeros((B, T, hop + 1, 2), np.float32)
+        lib.check(lib.dn_stft_general(dsp, emu.ptr(x), emu.ptr(spec), None, B, L, None))
+        ref = dsp_np64.stft(x, n_fft, hop, window=w)
+        assert ref.shape == (B, hop + 1, T)
+        err = np.abs(dc.cplx(spec) - ref)
+        assert err.max() <= stft_bar(ref), (L, "max-abs error per column " + ", ".join(f"{err[:, :, t].max():.2e}" for t in range(T)))
+        # the inverse of the REFERENCE spectrum (fp32 values), so that the two kernels are checked apart
+        ref32 = dc.ri(ref)
+        wave = np.zeros((B, hop * (T - 1)), np.float32)
+        lib.check(lib.dn_istft_general(dsp, emu.ptr(ref32), emu.ptr(wave), B, T, None))
+        want = dsp_np64.istft(dc.cplx(ref32), n_fft, hop, window=w)
+        assert want.shape == wave.shape
+        rms, mx, scale = dc.wave_errors(wave, want)
+        err = np.abs(wave - want)
+        per_hop = ", ".join(f"{err[:, k * hop:(k + 1) * hop].max():.2e}" for k in range(T - 1))
+        assert mx <= TOL_ROUND_TRIP * scale, (L, f"max-abs error per output hop {per_hop}; sample 0 {err[:, 0].max():.2e}")
+
+
+# ------------------------------------------------------------------ Griffin-Lim
+def _griffinlim(lib, dsp, n_fft, w, n_iter, momentum, B=2):
+    mag, init = dc.magnitudes(B, n_fft, 400 + n_fft + n_iter)
+    wave = np.zeros((B, n_fft), np.float32)
+    lib.check(lib.dn_griffinlim(dsp, emu.ptr(emu.f32(mag.transpose(0, 2, 1))), emu.ptr(dc.ri(init)), 0, 0, None, emu.ptr(wave), B, n_iter,
+                                momentum, None))
+    ref = dsp_np64.griffinlim(mag, n_fft, n_fft // 2, init, n_iter=n_iter, momentum=momentum, window=w)
+    return wave_close(wave, ref, n_fft, f"dn_griffinlim n_iter {n_iter} momentum {momentum}")
+
+
+@pytest.mark.parametrize("n_fft,name", CASES, ids=IDS)
+def test_griffinlim_with_the_window_at_other_iteration_counts_and_momenta(lib, plans, n_fft, name):
+    """Injected phases; n_iter 0 is istft of the phased magnitudes, 1 the first re-STFT (no momentum term yet), then momentum 0.5 and 0."""
+    dsp, w = plans(n_fft, name), dc.window(name, n_fft)
+    for n_iter, momentum in ((0, 0.99), (1, 0.99), (5, 0.5), (6, 0.0)):
+        _griffinlim(lib, dsp, n_fft, w, n_iter, momentum)
+
+
+def test_griffinlim_32_iterations_with_the_asymmetric_window(lib, plans):
+    _griffinlim(lib, plans(1024, "asym"), 1024, dc.window("asym", 1024), 32, 0.99)
+
+
+# ------------------------------------------------------------------ the fused hop and the stream step
+@pytest.mark.parametrize("n_fft,name", CASES, ids=IDS)
+def test_process_frame_and_two_stream_steps_with_the_window(lib, plans, model, n_fft, name):
+    """dn_stft_mel_log1p, dn_process_frame and two chained dn_stream_steps (ring, overlap-add line, hx carried) against process_frame64
+    with the window; 64 mels, four Griffin-Lim iterations."""
+    dsp, p, w, B, n_iter = plans(n_fft, name), geometry(n_fft), dc.window(name, n_fft), 2, 4
+    sig = dc.noise((B, n_fft + p.hop), 500 + n_fft, dc.HOP_LEVEL)
+    g = np.random.default_rng(600 + n_fft)
+    inits = [(g.random((B, p.n_stft, 3)) + 1j * g.random((B, p.n_stft, 3))).astype(np.complex64) for _ in range(2)]
+    emitted, hx64 = dc.stream64(sig, inits, p, w, n_iter)
+    (first,), hx1 = dc.frames64([sig[:, :n_fft]], inits[:1], p, w, n_iter)
+    from oracle import pipeline_np64
+    r0 = pipeline_np64.process_frame64(sig[:, :n_fft], np.zeros((B, 17, 4)), dc.model64(), w, dc.fbank(p), inits[0], n_fft, p.hop, n_iter=0)
+    # log-mel of the front half
+    mel = np.zeros((B, 3, p.n_mels), np.float32)
+    lib.check(lib.dn_stft_mel_log1p(dsp, emu.ptr(emu.f32(sig[:, :n_fft])), emu.ptr(mel), None, B, DN_PEAK_NORMALIZE | DN_PRE_WINDOW, None))
+    assert np.abs(mel - r0["model_input"]).max() <= TOL_LOGMEL
+    # the whole hop
+    ws = np.zeros(lib.dn_workspace_bytes(dsp, B) // 4 + 16, np.float32)
+    hx = np.zeros((B, 17, 4), np.float32)
+    out = np.zeros((B, n_fft), np.float32)
+    resid = np.zeros((B, 3, p.n_mels), np.float32)
+    lib.check(lib.dn_process_frame(model, dsp, emu.ptr(emu.f32(sig[:, :n_fft])), emu.ptr(hx), emu.ptr(out), emu.ptr(resid),
+                                   emu.ptr(dc.ri(inits[0])), 0, 0, n_iter, 0.99, emu.ptr(ws), B, 0, None))
+    assert np.abs(hx - hx1).max() <= TOL_RESIDUAL
+    assert np.abs(resid - (r0["predicted_diff"])).max() <= TOL_RESIDUAL
+    wave_close(out, first, n_fft, "dn_process_frame")
+    # the stream: the first hop primes the ring, two steps run frames 0 and 1
+    ring = np.zeros((B, n_fft), np.float32)
+    ring[:, p.hop:] = sig[:, :p.hop]
+    ola = np.zeros((B, n_fft), np.float32)
+    hx = np.zeros((B, 17, 4), np.float32)
+    got = []
+    for k in range(2):
+        hop_in = emu.f32(sig[:, (k + 1) * p.hop:(k + 2) * p.hop])
+        hop_out = np.zeros((B, p.hop), np.float32)
+        lib.check(lib.dn_stream_step(model, dsp, emu.ptr(hop_in), emu.ptr(ring), emu.ptr(ola), emu.ptr(hx), emu.ptr(hop_out),
+                                     emu.ptr(dc.ri(inits[k])), 0, 0, n_iter, 0.99, emu.ptr(ws), B, 0, None))
+        got.append(hop_out)
+    assert not got[0].any() and np.abs(emitted[:, p.hop:]).max() > 0.1
+    wave_close(got[1], emitted[:, p.hop:], n_fft, "second stream step")
+    assert np.abs(hx - hx64).max() <= TOL_RESIDUAL
+    # what the second step leaves on the overlap-add line: frame 0's second half + frame 1's first half, then frame 1's second half
+    outs64, _ = dc.frames64([sig[:, :n_fft], sig[:, p.hop:]], inits, p, w, n_iter)
+    line = np.concatenate([outs64[0][:, p.hop:] + outs64[1][:, :p.hop], outs64[1][:, p.hop:]], axis=1)
+    wave_close(ola, line, n_fft, "overlap-add line after two steps")
+
+
+# ------------------------------------------------------------------ n_fft 1024: the schedules that read the host-built tables
+P64 = pipeline_ref.Params(16000, 1024, 512, 64)
+N_HOPS, N_ITER = 4, 4
+
+
+@pytest.fixture(scope="module")
+def chains(lib, plans, model):
+    """window name -> (signal dict, injected phases as the kernels store them, the wave-per-column pipe's frames + hx, the float64 frames + hx)
+    for N_HOPS chained hops of two streams, computed once per window"""
+    made = {}
+
+    def get(name):
+        if name not in made:
+            B = 2
+            g = {"signal": dc.noise((B, 1024 + (N_HOPS - 1) * 512), 700, dc.HOP_LEVEL)}
+            rg = np.random.default_rng(701)
+            inits = [(rg.random((B, 513, 3)) + 1j * rg.random((B, 513, 3))).astype(np.complex64) for _ in range(N_HOPS)]
+            init = [dc.ri(a) for a in inits]
+            a = _run_pipe(lib, plans(1024, name), model, DN_GL_WAVE_PER_COLUMN, B, N_HOPS, g, init=init, n_iter=N_ITER, P=P64)
+            frames = [np.ascontiguousarray(g["signal"][:, h * 512:h * 512 + 1024]) for h in range(N_HOPS)]
+            made[name] = (g, init, a, dc.frames64(frames, inits, P64, dc.window(name, 1024), N_ITER), inits)
+        return made[name]
+    return get
+
+
+def _same_and_close_to_float64(b, chain):
+    _, _, a, (outs64, hx64), _ = chain
+    assert len(a) == len(b) == N_HOPS + 1
+    for h, (x, y) in enumerate(zip(a, b)):
+        assert np.array_equal(x, y), h
+    for h in range(N_HOPS):
+        wave_close(b[h], outs64[h], 1024, f"hop {h}")
+    assert np.abs(b[-1] - hx64).max() <= TOL_RESIDUAL
+
+
+@pytest.mark.parametrize("name", dc.WINDOWS)
+def test_wave_per_stream_pipe_and_depth_two_with_the_window(lib, plans, model, chains, name):
+    """The one-hop pipe with DN_GL_WAVE_PER_STREAM forced and the depth-2 pipe (chain segments, wave per stream): the wave-per-column pipe's
+    frames and hx bit for bit, as under Hann -- and, which the schedules' identity alone cannot show, float64's."""
+    g, init, a, _, _ = chain = chains(name)
+    _same_and_close_to_float64(a, chain)             # (the wave-per-column pipe itself against float64)
+    b = _run_pipe(lib, plans(1024, name), model, DN_GL_WAVE_PER_STREAM, 2, N_HOPS, g, init=init, n_iter=N_ITER, P=P64)
+    _same_and_close_to_float64(b, chain)
+    b = _run_pipe(lib, plans(1024, name), model, DN_GL_AUTO, 2, N_HOPS, g, init=init, n_iter=N_ITER, depth=2, P=P64)
+    _same_and_close_to_float64(b, chain)
+
+
+@pytest.mark.parametrize("H", [2, 4])
+@pytest.mark.parametrize("name", dc.WINDOWS)
+def test_hop_groups_with_the_window(lib, plans, model, chains, name, H):
+    g, init, _, _, _ = chain = chains(name)
+    b = _run_groups(lib, plans(1024, name), model, 2, N_HOPS, g, H, init=init, n_iter=N_ITER, P=P64)
+    _same_and_close_to_float64(b, chain)
+
+
+@pytest.mark.parametrize("name", dc.WINDOWS)
+def test_session_pool_in_both_schedules_with_the_window(lib, plans, model, chains, name):
+    """Two sessions on scattered slots of a pool of four, one priming push and three frames each, injected phases: the one-launch and the
+    two-launch schedule against each other as under Hann (the host build of the fused inverse-mel prologue rounds differently: 1e-5) and
+    each against the float64 stream."""
+    g, init, _, _, inits = chains(name)
+    sig, F, slots = g["signal"], 3, [3, 1]
+    want, _ = dc.stream64(sig[:, :1024 + (F - 1) * 512], inits[:F], P64, dc.window(name, 1024), N_ITER)
+    got = {}
+    for schedule in (DN_SESS_ONE_LAUNCH, DN_SESS_TWO_LAUNCHES):
+        pool = Pool(lib, model, plans(1024, name), 4, schedule)
+        pool.open(slots, [11, 12])
+        outs = []
+        for t in range(F + 1):
+            ia = None if t == 0 else init[t - 1]
+            outs.append(pool.push(slots, emu.f32(sig[:, t * 512:(t + 1) * 512]), 0, n_iter=N_ITER, init=ia))
+        pool.destroy()
+        assert not outs[0].any() and not outs[1].any()
+        got[schedule] = np.concatenate(outs[1:], axis=1)
+        assert np.abs(want[:, 512:]).max() > 0.1
+        wave_close(got[schedule], want, 1024, f"sessions, schedule {schedule}")
+    assert np.abs(got[DN_SESS_ONE_LAUNCH] - got[DN_SESS_TWO_LAUNCHES]).max() <= 1e-5
