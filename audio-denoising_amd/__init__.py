@@ -13,4 +13,8 @@ def __getattr__(name):
     if name in ("SessionPool", "SessionState"):
         import importlib
         return getattr(importlib.import_module(__name__ + ".sessions"), name)
+    # ``audio_denoising_amd.Denoiser`` (``denoise_clip``: a whole clip per call) / ``DenoiserStream`` (``push`` / ``push_many``), likewise
+    if name in ("Denoiser", "DenoiserStream"):
+        import importlib
+        return getattr(importlib.import_module(__name__ + ".pipeline"), name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -881,6 +881,48 @@ int dn_stream_step(const dn_model* m, const dn_dsp* d, const float* hop_in, floa
     return check_launch("frame_kernel(stream)");
 }
 
+// ------------------------------------------------------------------ clip mode: N hops per call
+// frame rows | mel | residual | peak, in floats per frame (dn_clip.hip)
+static size_t clip_row_floats(const dn_dsp* d) { return d->cfg.n_fft == 1024 ? (size_t)dn::kClipRow1024 : (size_t)d->cfg.n_fft; }
+constexpr long long kClipMaxFrames = 1ll << 22;          // B x N of one call: every grid and every 32-bit index of the kernels stays in range
+
+size_t dn_clip_workspace_bytes(const dn_dsp* d, int32_t B, int32_t N) {
+    if (!d || B <= 0 || N <= 0 || d->cfg.n_mels <= 0 || (long long)B * N > kClipMaxFrames) return 0;
+    const size_t frames = (size_t)B * (size_t)N;
+    return ((frames * (clip_row_floats(d) + 6 * (size_t)d->cfg.n_mels + 1) * sizeof(float) + 255) & ~size_t(255)) + 256;
+}
+
+int dn_clip_process(const dn_model* m, const dn_dsp* d, const void* hops_in, int32_t in_s16, float* ring, float* ola, float* hx, void* hops_out,
+                    int32_t out_s16, const float* init_angles, uint64_t seed, uint64_t stream_id0, int32_t n_iter, float momentum,
+                    void* workspace, int32_t B, int32_t N, uint32_t flags, void* stream) {
+    // every argument is validated before the first launch, so a failed call leaves ring, ola and hx untouched
+    if (B < 1 || N < 1) return fail(DN_ERR_INVALID, "dn_clip_process: needs B >= 1 streams and N >= 1 hops");
+    if (!hops_in || !ring || !ola || !hx || !hops_out || !workspace) return fail(DN_ERR_INVALID, "dn_clip_process: null argument");
+    const uint32_t gl = flags & (uint32_t)(DN_CLIP_GL_PER_COLUMN | DN_CLIP_GL_PER_STREAM);
+    int rc = check_hop_args("dn_clip_process", m, d, B, n_iter, momentum, flags & ~gl);
+    if (rc != DN_OK) return rc;
+    if (gl == (uint32_t)(DN_CLIP_GL_PER_COLUMN | DN_CLIP_GL_PER_STREAM))
+        return fail(DN_ERR_INVALID, "dn_clip_process: DN_CLIP_GL_PER_COLUMN and DN_CLIP_GL_PER_STREAM exclude each other");
+    if ((gl & DN_CLIP_GL_PER_STREAM) && d->cfg.n_fft != 1024)
+        return fail(DN_ERR_UNSUPPORTED, "the wavefront-per-stream Griffin-Lim is built for n_fft 1024 (at 1536 the per-lane state of a stream does not fit a wavefront's registers; at 512 the schedule is not built)");
+    if ((long long)B * N > kClipMaxFrames)
+        return fail(DN_ERR_INVALID, "dn_clip_process: B x N exceeds " + std::to_string(kClipMaxFrames) + " frames a call (tile the clip)");
+    const int M = d->cfg.n_mels, C = M / 16;
+    BiasSet* bs = nullptr;
+    rc = build_bias(const_cast<dn_model*>(m), C, &bs);
+    if (rc != DN_OK) return rc;
+    dn::ClipArgs a{};
+    a.hops_in = hops_in; a.in_s16 = in_s16 != 0; a.ring = ring; a.ola = ola; a.hx = hx; a.hops_out = hops_out; a.out_s16 = out_s16 != 0;
+    a.init = init_angles; a.seed = seed; a.sid0 = stream_id0; a.n_iter = n_iter; a.mom = momentum / (1.0f + momentum);
+    a.C = C; a.B = B; a.N = N; a.n_fft = d->cfg.n_fft; a.n_mels = M;
+    a.frames = (size_t)B * (size_t)N;
+    a.fr = static_cast<float*>(workspace); a.fr_stride = clip_row_floats(d);
+    a.mel = a.fr + a.frames * a.fr_stride; a.diff = a.mel + a.frames * 3 * M; a.peak = a.diff + a.frames * 3 * M;
+    a.per_stream = d->cfg.n_fft == 1024 && ((gl & DN_CLIP_GL_PER_STREAM) || (gl == 0 && (long)a.frames >= dn::kClipGlwAutoFrames));
+    dn::launch_clip(d->view, bs->view_dev, a, (flags & DN_CONV_BF16) != 0, as_stream(stream));
+    return check_launch("dn_clip_process");
+}
+
 // ------------------------------------------------------------------ software-pipelined hops
 static size_t slot_floats(const dn_dsp* d, int32_t B) {
     return (size_t)B * (6 * (size_t)d->cfg.n_mels + 1 + dn::kSlotMeta + 3 * ((size_t)d->cfg.n_fft / 2 + 1));

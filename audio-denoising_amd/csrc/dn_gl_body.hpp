@@ -78,7 +78,9 @@ template <int NFFT> constexpr int gl_smem() { return gl_tiles<NFFT>() + 4 * 2 * 
 // EXIT_GE: how the loop tests for its last iteration.  Semantically the same (n_last >= it_begin); the compiler lays the loop out differently, and
 // measurably so at n_fft 1536 (256 registers, a few values in scratch): `==` suits the chain that runs to the end (115 -> 103 us per batch-256 hop),
 // `>=` the head start that stops early (its iterations 17.2 k -> 13.5 k ticks).  Each call site of dn_hop.hip uses what measured best.
-template <int NFFT, bool FROM_MEL, bool STREAM = false, bool EXIT_GE = false>
+// STAGE (with STREAM = false): store frame x 1/envelope, unscaled, to `wave` -- the rounded product the overlap-add's fma takes -- for a caller
+// that folds the frames of several hops of a stream afterwards (dn_clip.hip; kEmitStage of dn_glw_body.hpp, into memory).
+template <int NFFT, bool FROM_MEL, bool STREAM = false, bool EXIT_GE = false, bool STAGE = false>
 __device__ __forceinline__ void gl_body(char* smem, const DspDev& d, const float* __restrict__ mag,
                                         const float* __restrict__ diff, const v2f* __restrict__ init, uint64_t seed,
                                         uint64_t sid0, const float* __restrict__ scale, float* __restrict__ wave,
@@ -300,7 +302,7 @@ __device__ __forceinline__ void gl_body(char* smem, const DspDev& d, const float
             const float sc = scale != nullptr ? scale[b] : 1.0f;
             if (!STREAM) {
                 for (int n = tid; n < kNR; n += kGlThreads)
-                    wave[b * kNR + n] = (y1[n] + yo[n]) * d.inv_env[n] * sc;
+                    wave[b * kNR + n] = STAGE ? (y1[n] + yo[n]) * d.inv_env[n] : (y1[n] + yo[n]) * d.inv_env[n] * sc;
             } else {
                 constexpr int kR = (kNR + kGlThreads - 1) / kGlThreads;
                 float* orow = ola + b * kNR;

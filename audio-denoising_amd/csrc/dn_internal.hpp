@@ -229,6 +229,22 @@ void launch_sess_export(const SessArgs& a, const SessRec& r, int n_fft, void* re
 constexpr uint32_t kSessRecBadMagic = 1, kSessRecBadVersion = 2, kSessRecBadGeometry = 3, kSessRecBadPushes = 4;
 void launch_sess_check(const SessArgs& a, const SessRec& r, const void* records, uint32_t* status, hipStream_t st);
 void launch_sess_import(const SessArgs& a, const SessRec& r, int n_fft, const void* records, const uint64_t* sids_in, hipStream_t st);
+// N consecutive hops of B streams in one call (dn_clip.hip; dn_clip_process).  Frame f = b N + i is hop i of stream b.
+constexpr long kClipGlwAutoFrames = 1024;       // n_fft 1024: from this many frames (B x N) on a call runs its chains a wavefront per frame (measured, profiles/clip_time.txt: per column / per frame 0.87 at 256 frames, 1.03 at 1,024, 1.15 at 4,096, 1.28 at 24,000)
+constexpr int kClipRow1024 = 1540;               // floats of a frame row at n_fft 1024: the linear magnitudes [3][513], in whole 16-byte units (else n_fft: the samples)
+struct ClipArgs {
+    const void* hops_in; int in_s16;                            // [B][N hop] float32 or int16
+    float* ring; float* ola; float* hx;                         // [B][n_fft], [B][n_fft], [B][17][C]: advanced in place by N hops
+    void* hops_out; int out_s16;                                // [B][N hop] float32 or int16
+    const float* init;                                          // [B][N][3][K] complex initial phases, or null = device RNG
+    uint64_t seed, sid0; int n_iter; float mom;                 // hop i of stream b draws from (seed + i, sid0 + b)
+    int C, B, N, n_fft, n_mels;
+    size_t frames;                                              // B x N
+    float* fr; size_t fr_stride;                                // workspace: frame rows [B N][fr_stride]
+    float* mel; float* diff; float* peak;                       //            [B N][3][M], [B N][3][M], [B N]
+    int per_stream;                                             // chains a wavefront per frame (n_fft 1024) instead of a wavefront per column
+};
+void launch_clip(const DspDev& d, const CellDev* c_dev, const ClipArgs& a, bool bf16, hipStream_t st);
 void launch_cell_bf16(const CellDev& c, const float* x, const float* hx_in, float* out, float* hx_out, int B, int T,
                       int C, hipStream_t st);
 void launch_cell_ex(const CellDev& c, const float* x, const float* hx_in, float* out, float* hx_out, int B, int T,

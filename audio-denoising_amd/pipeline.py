@@ -41,6 +41,7 @@ class Denoiser:
         # ``window`` (n_fft,): what another ``window_fn`` would return; the reference passes torch.hann_window (app3.py:155)
         self.plan = DspPlan(self.device, sample_rate, n_fft, hop_length, n_mels, fb=fb, window=torch.hann_window(n_fft) if window is None else window)
         self._ws = None
+        self._clip_ws = None
         self._calls = 0
 
     def _flags(self) -> int:
@@ -108,6 +109,80 @@ class Denoiser:
                                                      None if resid is None else resid.data_ptr(), ia_ptr, seed, stream_id0,
                                                      self.n_iter, self.momentum, ws.data_ptr(), B, self._flags(), st))
         return (out, hx_new, resid) if return_residual else (out, hx_new)
+
+    # -- clip mode: N hops per call
+    CLIP_FRAME_CAP = 65536          # frames (streams x hops) one dn_clip_process call carries at most: ~8 KB of workspace a frame at n_fft 1024
+
+    def clip_hops(self, length: int) -> int:
+        """Hops ``denoise_clip`` runs for a clip of ``length`` samples: the whole hops that cover it plus the one that drains the overlap-add line
+        (its ``init_angles`` has one set of phases per hop)."""
+        return -(-int(length) // self.hop) + 1
+
+    def _pack_clip_angles(self, per_hop, batch: int, n0: int, n: int):
+        """hops n0 .. n0 + n of a sequence of (B, K, 3) complex64 -> [B][n][3][K] interleaved storage."""
+        if per_hop is None:
+            return None
+        hops = [per_hop[n0 + i] for i in range(n)]
+        for ia in hops:
+            if tuple(ia.shape) != (batch, self.n_stft, 3) or ia.dtype != torch.complex64:
+                raise ValueError(f"init_angles must be complex64 of shape {(batch, self.n_stft, 3)} per hop")
+        z = torch.stack([ia.to(self.device) for ia in hops], dim=1)          # (B, n, K, 3)
+        return torch.view_as_real(z.transpose(-1, -2).contiguous())
+
+    def _clip(self, hops_in: torch.Tensor, ring: torch.Tensor, ola: torch.Tensor, hx: torch.Tensor, init_angles_per_hop, seed: int,
+              stream_id0: int, frame_cap: int | None = None, gl: int = 0) -> torch.Tensor:
+        """``hops_in`` (B, N * hop) float32 or int16 through dn_clip_process in tiles of at most ``frame_cap`` frames: exactly N ``dn_stream_step``
+        calls on (ring, ola, hx), hop i with ``seed + i``; returns the (B, N * hop) samples they emit, in the dtype of ``hops_in``."""
+        B, n_hops = hops_in.shape[0], hops_in.shape[1] // self.hop
+        cap = self.CLIP_FRAME_CAP if frame_cap is None else int(frame_cap)
+        if cap < 1:
+            raise ValueError("the frame cap must be positive")
+        per_call = max(1, cap // B)
+        s16 = hops_in.dtype == torch.int16
+        out = torch.empty_like(hops_in)
+        model_h = self.model._native(self.device)
+        with torch.cuda.device(self.device):
+            st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+            for n0 in range(0, n_hops, per_call):
+                n = min(per_call, n_hops - n0)
+                whole = n == n_hops
+                tin = hops_in if whole else hops_in[:, n0 * self.hop:(n0 + n) * self.hop].contiguous()
+                tout = out if whole else torch.empty_like(tin)
+                ia = self._pack_clip_angles(init_angles_per_hop, B, n0, n)
+                need = self.lib.dn_clip_workspace_bytes(self.plan.handle, B, n)
+                if self._clip_ws is None or self._clip_ws.numel() < need:
+                    self._clip_ws = torch.empty(need, dtype=torch.uint8, device=self.device)
+                self.lib.check(self.lib.dn_clip_process(model_h, self.plan.handle, tin.data_ptr(), int(s16), ring.data_ptr(), ola.data_ptr(),
+                                                        hx.data_ptr(), tout.data_ptr(), int(s16), None if ia is None else ia.data_ptr(),
+                                                        seed + n0, stream_id0, self.n_iter, self.momentum, self._clip_ws.data_ptr(), B, n,
+                                                        self._flags() | gl, st))
+                if not whole:
+                    out[:, n0 * self.hop:(n0 + n) * self.hop] = tout
+        return out
+
+    def denoise_clip(self, wave: torch.Tensor, seed: int = 0, stream_id0: int = 0, init_angles=None, frame_cap: int | None = None) -> torch.Tensor:
+        """Offline: ``wave`` (B, L) float32 or int16 PCM on the device -> the denoised clips, same shape and dtype, output sample n lined up with
+        input sample n.  What a fresh ``DenoiserStream`` emits for the clip -- the first hop primes the ring, the clip is zero-padded to whole
+        hops plus the two that drain the overlap-add line, the first emitted hop (the zeros of the empty line) is dropped -- computed by
+        ``dn_clip_process``: all frames analysed at once, the model hop by hop, every Griffin-Lim chain side by side.  Hop i of stream b draws
+        its phases from ``(seed + i, stream_id0 + b)``, or takes ``init_angles[i]`` (B, K, 3) complex64, ``clip_hops(L)`` of them."""
+        if wave.dim() != 2 or wave.device != self.device or wave.dtype not in (torch.float32, torch.int16):
+            raise ValueError(f"wave must be float32 or int16 (B, L) on {self.device}")
+        B, L = wave.shape
+        if B == 0 or L == 0:
+            return torch.empty_like(wave)
+        n_hops = self.clip_hops(L)
+        if init_angles is not None and len(init_angles) != n_hops:
+            raise ValueError(f"init_angles: one set of phases for each of the {n_hops} hops")
+        padded = torch.zeros(B, (n_hops + 1) * self.hop, dtype=wave.dtype, device=self.device)
+        padded[:, :L] = wave
+        ring = torch.zeros(B, self.n_fft, dtype=torch.float32, device=self.device)
+        first = padded[:, :self.hop]
+        # (int16 -> float32 as the kernels do it: a true division, by a tensor -- a Python scalar would become a multiplication by its reciprocal)
+        ring[:, self.hop:] = first.float() / torch.tensor(32767.0, device=self.device) if wave.dtype == torch.int16 else first
+        ola = torch.zeros_like(ring)
+        out = self._clip(padded[:, self.hop:].contiguous(), ring, ola, self.init_hx(B), init_angles, seed, stream_id0, frame_cap)
+        return out[:, self.hop:self.hop + L].contiguous()
 
     def process_frame_(self, frames: torch.Tensor, hx: torch.Tensor, out: torch.Tensor, seed: int = 0, stream_id0: int = 0) -> None:
         """Allocation-free variant for steady-state loops and hipGraph capture: ``hx`` is advanced in place and
@@ -693,8 +768,9 @@ class DenoiserStream:
     samples are buffered, return the emitted output samples.  No added latency (one launch per hop,
     ``dn_stream_step``); frame f's Griffin-Lim draws from ``seed + f``."""
 
-    def __init__(self, denoiser: Denoiser, batch: int, stream_id0: int = 0, seed: int = 0):
+    def __init__(self, denoiser: Denoiser, batch: int, stream_id0: int = 0, seed: int = 0, clip_frame_cap: int | None = None):
         self.dn, self.batch, self.stream_id0, self.seed = denoiser, batch, stream_id0, seed
+        self.clip_frame_cap = clip_frame_cap          # frames per dn_clip_process call of push_many (None: Denoiser.CLIP_FRAME_CAP)
         d = denoiser
         dev = d.device
         self.ring = torch.zeros(batch, d.n_fft, dtype=torch.float32, device=dev)
@@ -736,3 +812,28 @@ class DenoiserStream:
         if not outs:
             return torch.zeros(self.batch, 0, dtype=torch.float32, device=d.device)
         return torch.cat(outs, dim=1)
+
+    def push_many(self, chunk: torch.Tensor, init_angles_per_hop=None, frame_cap: int | None = None) -> torch.Tensor:
+        """``push`` for a caller that holds many hops at once (a recorded file, a backlog): same contract, same samples and state bit for bit,
+        but every whole hop waiting goes through ``dn_clip_process`` -- a fixed number of launches per call instead of one per hop, the
+        Griffin-Lim chains of all hops side by side -- in tiles of at most ``frame_cap`` frames (streams x hops; default: the constructor's
+        ``clip_frame_cap``, else ``Denoiser.CLIP_FRAME_CAP``)."""
+        d = self.dn
+        if chunk.device != d.device or chunk.dtype != torch.float32 or chunk.shape[0] != self.batch:
+            raise ValueError("chunk must be float32 (B, n) on the denoiser's device")
+        self.pending = torch.cat([self.pending, chunk], dim=1)
+        prime = d.n_fft - d.hop
+        if self.filled < prime:
+            take = min(prime - self.filled, self.pending.shape[1])
+            self.ring[:, d.hop + self.filled: d.hop + self.filled + take] = self.pending[:, :take]
+            self.pending = self.pending[:, take:]
+            self.filled += take
+        n_hops = self.pending.shape[1] // d.hop if self.filled == prime else 0
+        if n_hops == 0:
+            return torch.zeros(self.batch, 0, dtype=torch.float32, device=d.device)
+        hops_in = self.pending[:, :n_hops * d.hop].contiguous()
+        self.pending = self.pending[:, n_hops * d.hop:]
+        out = d._clip(hops_in, self.ring, self.ola, self.hx, init_angles_per_hop, self.seed + self.hops, self.stream_id0,
+                      self.clip_frame_cap if frame_cap is None else frame_cap)
+        self.hops += n_hops
+        return out

@@ -26,6 +26,7 @@
  *   dn_stft_general / dn_server_rows / dn_istft_general / dn_cell_forward_ex   server.py:199-217  the socket server's variant
  *   dn_process_frame                    app3.py:178-217  the whole per-hop loop body for B streams
  *   dn_stream_step                      app3.py:178-226  the same plus ring buffer / overlap-add state (P12)
+ *   dn_clip_process                     app3.py:178-226  N consecutive dn_stream_step calls in one: audio that is already there
  *   dn_sessions_*                       app3.py:123-250  one DenoisingAudioProcessor per session: slots that join, leave
  *                                       and push hops on their own, batched per tick; sessions exported to and
  *                                       imported from self-contained records (move, resume, resize a pool)
@@ -54,7 +55,7 @@
 extern "C" {
 #endif
 
-#define DN_ABI_VERSION 6
+#define DN_ABI_VERSION 7
 
 typedef enum dn_status {
     DN_OK = 0,
@@ -235,6 +236,30 @@ int dn_process_frame(const dn_model* m, const dn_dsp* d, const float* frames, fl
 int dn_stream_step(const dn_model* m, const dn_dsp* d, const float* hop_in, float* ring, float* ola, float* hx,
                    float* hop_out, const float* init_angles, uint64_t seed, uint64_t stream_id0, int32_t n_iter,
                    float momentum, void* workspace, int32_t B, uint32_t flags, void* stream);
+
+/* ---- Clip mode: N hops per call --------------------------------------------------------------------
+ * For a caller that already holds the audio (a recorded file, a buffered upload, a backlog): exactly N consecutive
+ * dn_stream_step calls for B streams, hop i with seed + i -- the same hops out, ring, ola and hx, bit for bit -- as a fixed
+ * number of launches, whatever N: the analysis of all B x N frames at once, the N model forwards of a stream back to back
+ * in one workgroup (hx is the only chain from hop to hop), all B x N Griffin-Lim chains side by side over the whole GPU,
+ * then the overlap-add across hops.  No call synchronises.
+ *   hops_in  [dev][B][N*hop]  float32, or int16 PCM (x / 32767) when in_s16
+ *   ring, ola [dev][B][n_fft], hx [dev][B][17][C]: the stream state of dn_stream_step, advanced in place by N hops
+ *   hops_out [dev][B][N*hop]  float32, or int16 (clip, * 32767, truncate) when out_s16; must not overlap hops_in
+ *   init_angles [dev][B][N][3][K] complex or NULL (NULL: hop i of stream b draws from (seed + i, stream_id0 + b))
+ *   workspace [dev] of dn_clip_workspace_bytes(d, B, N) bytes, 16-byte aligned: (n_fft + 6 M + 1) floats a frame
+ *   (1540 + 6 M + 1 at n_fft 1024: ~8 KB at 80 mels), rounded up to 256 bytes, plus 256.
+ * All three transform sizes.  flags: DN_CONV_BF16, and at most one of the two below (both: DN_ERR_INVALID); with neither the
+ * library picks: n_fft 1024 runs a wavefront per frame from 1,024 frames (B x N) a call on, everything else a wavefront per
+ * column.  Either way the same bits.  Every argument is validated before the first launch (N >= 1, B >= 1, B x N <= 2^22), so a
+ * failed call leaves ring, ola and hx untouched. */
+#define DN_CLIP_GL_PER_COLUMN 2u   /* chains: one workgroup per frame, a wavefront per column (gl_body)            */
+#define DN_CLIP_GL_PER_STREAM 4u   /* chains: a wavefront per frame, four frames a workgroup (glw_body; n_fft 1024, else DN_ERR_UNSUPPORTED) */
+size_t dn_clip_workspace_bytes(const dn_dsp* d, int32_t B, int32_t N);
+int dn_clip_process(const dn_model* m, const dn_dsp* d, const void* hops_in, int32_t in_s16, float* ring, float* ola,
+                    float* hx, void* hops_out, int32_t out_s16, const float* init_angles, uint64_t seed,
+                    uint64_t stream_id0, int32_t n_iter, float momentum, void* workspace, int32_t B, int32_t N,
+                    uint32_t flags, void* stream);
 
 /* ---- Software-pipelined hops ------------------------------------------------------------------------
  * Consecutive hops depend on each other only through hx (the model); hop n's Griffin-Lim (~3/4 of a hop) is
