@@ -107,9 +107,9 @@ __device__ __forceinline__ void glw_body(char* smem, const DspDev& d, const floa
     v2f plo[3][kNP], phi[3][kNP], pmid[3];
     v2f snew[kNV];            // the rebuilt signal: sample pairs (2m, 2m+1), m = lane + 64 t
 
-    auto update = [mom](v2f reb, v2f& prev, v2f& x, float m) {      // as gl_body
+    auto update = [mom](v2f reb, const v2f& prev, v2f& next, v2f& x, float m) {      // as gl_body; `next` is the prev of the following iteration
         const v2f a = reb - prev * mom;
-        prev = reb;
+        next = reb;
         const float inv = __builtin_amdgcn_rsqf(fmaf(a[0], a[0], fmaf(a[1], a[1], 1e-32f)));
         x = a * (inv * m);
     };
@@ -266,12 +266,14 @@ __device__ __forceinline__ void glw_body(char* smem, const DspDev& d, const floa
         }
     }
 
-    for (int it = it_begin; it < it_last; ++it) {
-        if (it == it_begin + 1) DN_WSTAMP(4);
-        // ---- stft of the rebuilt signal (centre, reflect) -> phase update with momentum -> istft: the three columns as one skewed group of
-        // transforms in each direction (batch order 0, 2, 1).
-        // column 0: n0 < H -> s[H - n0], s[H - n0 - 1] (reflection), else the pair a hop earlier (same lane, register t - kHalf)
-        // column 2: n0 < H -> the pair a hop later (register t + kHalf), else s[3H - 2 - n0], s[3H - 3 - n0] (reflection)
+    // ---- one iteration: stft of the rebuilt signal (centre, reflect) -> phase update with momentum -> istft: the three columns as one skewed
+    // group of transforms in each direction (batch order 0, 2, 1).  The previous rebuilt spectra are read from one register set (pin) and the new
+    // ones are left in ANOTHER (pout): see the loop below.
+    // column 0: n0 < H -> s[H - n0], s[H - n0 - 1] (reflection), else the pair a hop earlier (same lane, register t - kHalf)
+    // column 2: n0 < H -> the pair a hop later (register t + kHalf), else s[3H - 2 - n0], s[3H - 3 - n0] (reflection)
+    using PP = v2f[3][kNP];
+    using PM = v2f[3];
+    auto iterate = [&](const PP& pin_lo, const PP& pin_hi, const PM& pin_mid, PP& pout_lo, PP& pout_hi, PM& pout_mid) __attribute__((always_inline)) {
         auto build0 = [&](v2f (&v)[kNV]) {
 #pragma unroll
             for (int t = 0; t < kNV; ++t) {
@@ -294,10 +296,10 @@ __device__ __forceinline__ void glw_body(char* smem, const DspDev& d, const floa
             rfft_split_pairs<kNV>(v, wkh, lane, rlo, rhi, rmid);
 #pragma unroll
             for (int t = 0; t < kNP; ++t) {
-                update(rlo[t], plo[c][t], xlo[t], mlo[c][t]);
-                update(rhi[t], phi[c][t], xhi[t], mhi[c][t]);
+                update(rlo[t], pin_lo[c][t], pout_lo[c][t], xlo[t], mlo[c][t]);
+                update(rhi[t], pin_hi[c][t], pout_hi[c][t], xhi[t], mhi[c][t]);
             }
-            update(rmid, pmid[c], xmid, mmid[c]);
+            update(rmid, pin_mid[c], pout_mid[c], xmid, mmid[c]);
         };
         v2f x0lo[kNP], x0hi[kNP], x0mid, x2lo[kNP], x2hi[kNP], x2mid, x1lo[kNP], x1hi[kNP], x1mid;
         {
@@ -312,6 +314,27 @@ __device__ __forceinline__ void glw_body(char* smem, const DspDev& d, const floa
             advance(v[2], std::integral_constant<int, 1>{}, x1lo, x1hi, x1mid);
         }
         synthesize(x0lo, x0hi, x0mid, x2lo, x2hi, x2mid, x1lo, x1hi, x1mid);
+    };
+    // The loop runs TWO iterations a trip and the two register sets of previous spectra swap roles: the rebuilt spectrum of one iteration IS the
+    // previous spectrum of the next, by name.  (One iteration a trip carries `prev = reb` round the back edge: the rebuilt bin is formed while the
+    // previous one is still live, so it cannot be formed in place, and the compiled loop ended in 54 register copies a lane and iteration.)  An odd
+    // count leaves one iteration behind the loop, which hands its spectra back to the first set -- copies once a segment, not once an iteration --
+    // so that whatever follows (park_segment, the next segment, the emit modes) finds the chain where it always was, on either parity.
+    v2f qlo[3][kNP], qhi[3][kNP], qmid[3];
+    int it = it_begin;
+    for (; it + 1 < it_last; it += 2) {
+        iterate(plo, phi, pmid, qlo, qhi, qmid);
+        if (it == it_begin) DN_WSTAMP(4);             // (the top of the segment's second iteration)
+        iterate(qlo, qhi, qmid, plo, phi, pmid);
+    }
+    if (it < it_last) {
+        iterate(plo, phi, pmid, qlo, qhi, qmid);
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+#pragma unroll
+            for (int t = 0; t < kNP; ++t) { plo[c][t] = qlo[c][t]; phi[c][t] = qhi[c][t]; }
+            pmid[c] = qmid[c];
+        }
     }
     if (park) {          // hand the chain over (uniform)
         DN_WSTAMP(5);
