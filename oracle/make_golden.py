@@ -55,10 +55,36 @@ def load_reference(gruunet2, name: str, num_compressed_bins: int):
     return m, ck
 
 
+SYNTH_SEED = 7
+
+
+def write_synth_fixture(cls, config, ref_module, blob, num_compressed_bins, n_bins, name, B=2, T=3):
+    """Run the reference class `cls` (built from a checkpoint's config, loaded with the synthetic `blob`) on seeded signed inputs in fp32 and
+    in float64; check the restatement `ref_module` against both (1e-5 / 1e-12); write blob, inputs and the four outputs.  Data only."""
+    sd = ref_module.unflatten_weights(blob)
+    cfg = dict(config)
+    cfg["num_compressed_bins"] = num_compressed_bins
+    rng = np.random.default_rng(SYNTH_SEED)
+    x = torch.from_numpy(rng.uniform(-6.0, 6.0, (B, T, n_bins)).astype(np.float32))
+    hidden = sd["cell.reset_gate.downs.0.conv.weight"].shape[0] // 3
+    hx = torch.from_numpy((0.5 * rng.standard_normal((B, hidden, num_compressed_bins))).astype(np.float32))
+    save = dict(blob=blob, x=x.numpy(), hx0=hx.numpy())
+    for dtype, tag, tol in ((torch.float32, "", 1e-5), (torch.float64, "_f64", 1e-12)):
+        m = cls(**cfg)
+        m.load_state_dict(sd)
+        m = m.eval().to(dtype)
+        with torch.no_grad():
+            out, hx1 = m(x.to(dtype), hx.to(dtype))
+            out2, hx2 = ref_module.forward({k: v.to(dtype) for k, v in sd.items()}, x.to(dtype), hx.to(dtype))
+        assert (out - out2).abs().max().item() <= tol and (hx1 - hx2).abs().max().item() <= tol, (name, tag)
+        save["out" + tag], save["hx1" + tag] = out.numpy(), hx1.numpy()
+    np.savez(os.path.join(GOLD, name), **save)
+
+
 def main():
     os.makedirs(GOLD, exist_ok=True)
     gruunet2 = import_reference_model()
-    from oracle import dsp_ref, model_ref, pipeline_ref
+    from oracle import dsp_ref, model_ref, pipeline_ref, synth_weights
 
     # ---- G1: weights -------------------------------------------------------
     manifest = {}
@@ -130,6 +156,13 @@ def main():
             o, hx = m(xs[h], hx)
             outs.append(o)
     np.savez(os.path.join(GOLD, "cell_dari_tult_chain20_F80.npz"), x=xs.numpy(), out=torch.stack(outs).numpy(), hx_final=hx.numpy())
+
+    # ---- G2b: the reference's own class loaded with a SYNTHETIC blob whose three offset buffers differ and have a spacing != 0.2
+    # (oracle/synth_weights.py), on signed inputs: pins what the restatement does with loaded offsets (coeff stays the constructor's,
+    # gruunet2.py:62-63), in fp32 and with the class cast to float64
+    write_synth_fixture(gruunet2.GRUUNet2, torch.load(os.path.join(REF, "saves", "GRUUNet2-dari_tult", "checkpoint.pth"), map_location="cpu",
+                                                      weights_only=True)["config"], model_ref, synth_weights.gruunet2_blob(SYNTH_SEED, "spacing"),
+                        5, 80, "cell_synth_B2_T3_F80.npz")
 
     # ---- G3: smear tables from the reference's GaussianSmearing ---------------
     gs = gruunet2.GaussianSmearing(num_gaussians=6)

@@ -17,6 +17,7 @@ REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLD = os.path.join(REPO, "tests", "golden")
 REF = "/root/reference"
 sys.path.insert(0, REPO)
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
 
 def main():
@@ -68,6 +69,11 @@ def main():
             outs.append(o)
     np.savez(os.path.join(GOLD, "momo3_conventions.npz"), x2=x2.numpy(), out2=o2.numpy(), hx2=h2.numpy(),
              xs=xs.numpy(), outs=torch.stack(outs).numpy(), hx_final=hx.numpy())
+    # the reference's own class loaded with a synthetic blob (two different offset buffers, spacing != 0.2), signed inputs, fp32 and float64
+    import make_golden
+    from oracle import synth_weights
+    make_golden.write_synth_fixture(momo3.MOMO3, cfg, momo_ref, synth_weights.momo3_blob(make_golden.SYNTH_SEED, "spacing"), 3, 22,
+                                    "momo3_synth_B2_T3_F22.npz")
     for fn in sorted(os.listdir(GOLD)):
         if "momo3" in fn:
             print(f"  {fn:40s} {os.path.getsize(os.path.join(GOLD, fn)):>9d} B")

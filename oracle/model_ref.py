@@ -64,9 +64,12 @@ def unflatten_weights(blob: torch.Tensor) -> dict:
 
 def smear_table(offset: torch.Tensor, length: int) -> torch.Tensor:
     """(G, L) Gaussian position code.  gruunet2.py:54-68 with the call pattern
-    of gruunet2.py:139-142: distances are fp32 linspace(0,1,L); coeff is
-    computed from the fp32 offset difference through .item()."""
-    coeff = -0.5 / (offset[1] - offset[0]).item() ** 2
+    of gruunet2.py:139-142: distances are fp32 linspace(0,1,L).  coeff is the
+    CONSTRUCTOR's (gruunet2.py:62-63): from its own fp32 linspace(0, 1, G)
+    through .item(), never recomputed after load_state_dict -- the loaded
+    ``offset`` buffer enters only in ``dist - offset``."""
+    ctor = torch.linspace(0.0, 1.0, offset.numel())
+    coeff = -0.5 / (ctor[1] - ctor[0]).item() ** 2
     pos = torch.linspace(0, 1, length).to(offset.dtype)
     d = pos.view(-1, 1) - offset.view(1, -1)            # (L, G)
     return torch.exp(coeff * torch.pow(d, 2)).t()       # (G, L)
@@ -78,11 +81,24 @@ def _with_smear(x: torch.Tensor, offset: torch.Tensor) -> torch.Tensor:
     return torch.cat((x, s.unsqueeze(0).expand(x.size(0), -1, -1)), dim=-2)
 
 
-def cell_step(sd: dict, x_t: torch.Tensor, hx: torch.Tensor, intermediates: dict | None = None):
+def cell_step(sd: dict, x_t: torch.Tensor, hx: torch.Tensor, intermediates: dict | None = None, mfma_round=None):
     """One GRUUNetCell.forward (gruunet2.py:228-244).
 
     x_t (B, F) ; hx (B, H, C) -> out (B, F), h' (B, H, C)
+
+    ``mfma_round`` (not in the reference; the yardstick of the bf16 conv tiles): a rounding function applied to the DATA channels of
+    the inputs and weights of encoder levels 0-3 and decoder levels 0-2, the convs that run on reduced-precision tiles.  The
+    position-code channels (folded into fp32 bias tables by the kernels), the hidden-gate conv, the GRU maths and the last decoder
+    level stay unrounded.
     """
+    def rounded(x, w, transposed):
+        if mfma_round is None:
+            return x, w
+        cd = x.size(1)
+        if transposed:
+            return mfma_round(x), torch.cat((mfma_round(w[:cd]), w[cd:]), 0)
+        return mfma_round(x), torch.cat((mfma_round(w[:, :cd]), w[:, cd:]), 1)
+
     off_in = sd["cell.input_gate.gs.offset"]
     off_rs = sd["cell.reset_gate.gs.offset"]
     off_out = sd["cell.output_gate.gs.offset"]
@@ -92,7 +108,8 @@ def cell_step(sd: dict, x_t: torch.Tensor, hx: torch.Tensor, intermediates: dict
     for lvl in range(4):
         w = sd[f"cell.input_gate.downs.{lvl}.conv.weight"]
         b = sd[f"cell.input_gate.downs.{lvl}.conv.bias"]
-        res.append(F.relu(F.conv1d(_with_smear(res[-1], off_in), w, b, stride=2, padding=1)))
+        xin, w = rounded(res[-1], w, False)
+        res.append(F.relu(F.conv1d(_with_smear(xin, off_in), w, b, stride=2, padding=1)))
 
     # hidden gates: relu(conv1d k3 s1 p1)                   gruunet2.py:145-155
     gate_h = F.relu(F.conv1d(_with_smear(hx, off_rs),
@@ -115,7 +132,10 @@ def cell_step(sd: dict, x_t: torch.Tensor, hx: torch.Tensor, intermediates: dict
         w = sd[f"cell.output_gate.ups.{lvl}.conv.weight"]
         b = sd[f"cell.output_gate.ups.{lvl}.conv.bias"]
         s = skips[3 - lvl]
-        y = F.conv_transpose1d(_with_smear(h, off_out), w, b, stride=2, padding=1,
+        hin = h
+        if lvl < 3:
+            hin, w = rounded(h, w, True)
+        y = F.conv_transpose1d(_with_smear(hin, off_out), w, b, stride=2, padding=1,
                                output_padding=s.size(-1) - (2 * h.size(-1) - 1))
         h = y if lvl == 3 else torch.cat((F.relu(y), s), dim=-2)
     if intermediates is not None:
@@ -123,8 +143,10 @@ def cell_step(sd: dict, x_t: torch.Tensor, hx: torch.Tensor, intermediates: dict
     return h.squeeze(-2), hi
 
 
-def forward(sd: dict, x: torch.Tensor, hx: torch.Tensor | None = None, num_compressed_bins: int | None = None):
-    """GRUUNet2.forward (gruunet2.py:290-306): x (B,T,F) or (T,F)."""
+def forward(sd: dict, x: torch.Tensor, hx: torch.Tensor | None = None, num_compressed_bins: int | None = None,
+            intermediates: list | None = None):
+    """GRUUNet2.forward (gruunet2.py:290-306): x (B,T,F) or (T,F).  ``intermediates``: a list that receives one dict per time
+    step (d0..d3, gate_h, hi as cell_step fills it)."""
     two_d = x.dim() == 2
     if two_d:
         x = x.unsqueeze(0)
@@ -133,7 +155,10 @@ def forward(sd: dict, x: torch.Tensor, hx: torch.Tensor | None = None, num_compr
         hx = torch.zeros(x.size(0), 17, c, dtype=x.dtype, device=x.device)
     outs = []
     for x_t in x.unbind(1):
-        o, hx = cell_step(sd, x_t, hx)
+        inter = None if intermediates is None else {}
+        o, hx = cell_step(sd, x_t, hx, inter)
+        if intermediates is not None:
+            intermediates.append(inter)
         outs.append(o)
     out = torch.stack(outs, dim=1)
     if two_d:

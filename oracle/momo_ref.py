@@ -61,12 +61,13 @@ def _informed(x: torch.Tensor, offset: torch.Tensor) -> torch.Tensor:
     return torch.cat((x, s.unsqueeze(0).expand(x.size(0), -1, -1)), dim=-2)            # momo3.py:140-145
 
 
-def cell_step(sd: dict, x2: torch.Tensor, hx: torch.Tensor):
-    """One MOMOCell.forward (momo3.py:228-245): x2 (B, 2, F) = [x_t ; x_t - prev], hx (B, 16, C) -> out (B, F), h' (B, 16, C)."""
+def cell_step(sd: dict, x2: torch.Tensor, hx: torch.Tensor, paddings=PADDINGS, intermediates: dict | None = None):
+    """One MOMOCell.forward (momo3.py:228-245): x2 (B, 2, F) = [x_t ; x_t - prev], hx (B, 16, C) -> out (B, F), h' (B, 16, C).
+    ``paddings``: the three encoder paddings of the constructor (the decoder walks them backwards)."""
     res = [_informed(x2, sd["cell.input_gate.gs.offset"])]
     for lvl in range(3):
         res.append(F.relu(F.conv1d(res[-1], sd[f"cell.input_gate.downs.{lvl}.conv.weight"], sd[f"cell.input_gate.downs.{lvl}.conv.bias"],
-                                   stride=2, padding=PADDINGS[lvl])))
+                                   stride=2, padding=paddings[lvl])))
     gate_h = F.relu(F.conv1d(_informed(hx, sd["cell.reset_gate.gs.offset"]), sd["cell.reset_gate.downs.0.conv.weight"],
                              sd["cell.reset_gate.downs.0.conv.bias"], stride=1, padding=1))
     i_r, i_i, i_n = res[-1].chunk(3, 1)
@@ -79,24 +80,28 @@ def cell_step(sd: dict, x2: torch.Tensor, hx: torch.Tensor):
     h = hi
     for lvl in range(3):
         s = skips[2 - lvl]
-        pad = PADDINGS[::-1][lvl]
+        pad = tuple(paddings)[::-1][lvl]
         base = (h.size(-1) - 1) * 2 - 2 * pad + 3
         y = F.conv_transpose1d(h, sd[f"cell.output_gate.ups.{lvl}.conv.weight"], sd[f"cell.output_gate.ups.{lvl}.conv.bias"],
                                stride=2, padding=pad, output_padding=s.size(-1) - base)          # output_size = len(skip), momo3.py:185-187
         h = y if lvl == 2 else torch.cat((F.relu(y), s), dim=-2)
+    if intermediates is not None:
+        intermediates.update(d0=res[1], d1=res[2], d2=res[3], gate_h=gate_h, hi=hi)
     return h.squeeze(-2), hi
 
 
-def compressed_bins(F_bins: int) -> int:
+def compressed_bins(F_bins: int, paddings=PADDINGS) -> int:
     L = F_bins
-    for p in PADDINGS:
+    for p in paddings:
         L = (L + 2 * p - 3) // 2 + 1
     return L
 
 
-def forward(sd: dict, x: torch.Tensor, hx: torch.Tensor | None = None, prev: torch.Tensor | None = None, num_compressed_bins: int = 3):
+def forward(sd: dict, x: torch.Tensor, hx: torch.Tensor | None = None, prev: torch.Tensor | None = None, num_compressed_bins: int = 3,
+            paddings=PADDINGS, intermediates: list | None = None):
     """MOMO3.forward (momo3.py:300-324): x (B,T,F) or (T,F); prev (B,1,F) or None -> (out, hx).  Also returns the last frame
-    (what a caller must pass as `prev` to continue the sequence in another call)."""
+    (what a caller must pass as `prev` to continue the sequence in another call).  ``intermediates``: a list that receives one dict
+    per time step (d0, d1, d2, gate_h, hi)."""
     two_d = x.dim() == 2
     if two_d:
         x = x.unsqueeze(0)
@@ -107,7 +112,10 @@ def forward(sd: dict, x: torch.Tensor, hx: torch.Tensor | None = None, prev: tor
         x_t = x_t.unsqueeze(1)
         if prev is None:
             prev = x_t.clone()
-        o, hx = cell_step(sd, torch.cat([x_t, x_t - prev], -2), hx)
+        inter = None if intermediates is None else {}
+        o, hx = cell_step(sd, torch.cat([x_t, x_t - prev], -2), hx, paddings, inter)
+        if intermediates is not None:
+            intermediates.append(inter)
         prev = x_t.clone()
         outs.append(o)
     out = torch.stack(outs, dim=1)

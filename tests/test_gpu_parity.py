@@ -104,7 +104,7 @@ def test_native_library_is_the_in_tree_hip_build(dev):
         assert any("libdn_denoise.so" in ln for ln in f)
 
 
-CELL_CASES = sorted(os.path.basename(p) for p in glob.glob(os.path.join(GOLDEN, "cell_*_B*_T*_F*.npz")))
+CELL_CASES = sorted(os.path.basename(p) for p in glob.glob(os.path.join(GOLDEN, "cell_dari_tult*_B*_T*_F*.npz")))
 
 
 @pytest.mark.parametrize("name", CELL_CASES)
