@@ -1077,6 +1077,7 @@ int dn_pipe_set_group(dn_pipe* p, int32_t hops) {
     p->scratch = scratch; p->scratch_init = init;
     p->n_slots = n_slots;
     p->group = hops; p->group_pending = 0;
+    p->group_pushes = h.pushes;                     // single pushes, replays and restores before this count towards priming: the control block is the record
     p->gl_split = 0;
     h.slot_next = 0;
     DN_HIP(hipMemcpy(p->ctl, &h, sizeof(h), hipMemcpyHostToDevice));
@@ -1091,6 +1092,8 @@ int dn_pipe_set_gl_schedule(dn_pipe* p, int32_t schedule) {
         return fail(DN_ERR_UNSUPPORTED, "the wavefront-per-stream Griffin-Lim is built for n_fft 1024 (at 1536 the per-lane state of a stream does not fit a wavefront's registers; at 512 the schedule is not built)");
     if (schedule == DN_GL_WAVE_PER_COLUMN && p->depth > 1)
         return fail(DN_ERR_INVALID, "a pipe deeper than one hop runs a wavefront per stream and chain segment");
+    if (schedule == DN_GL_WAVE_PER_COLUMN && p->group > 0)
+        return fail(DN_ERR_INVALID, "a group pipe runs whole chains a wavefront per stream (dn_pipe_set_group(p, 0) first)");
     p->gl_schedule = schedule;
     return DN_OK;
 }
@@ -1233,7 +1236,10 @@ int dn_pipe_stream_push(dn_pipe* p, const void* hop_in, int32_t in_is_s16, void*
     a.hop_in = hop_in; a.ring = p->ring; a.in_s16 = in_is_s16;
     a.ola = p->ola; a.hop_out = hop_out; a.out_s16 = out_is_s16;
     dn::launch_hop(p->d->view, p->bs->view, a, p->bf16, as_stream(stream));
-    return check_launch("hop_kernel(stream)");
+    rc = check_launch("hop_kernel(stream)");
+    if (rc != DN_OK) return rc;
+    ++p->group_pushes;              // (what *hops_valid of a later group flush charges to priming; the host-buffer pushes come through here too)
+    return DN_OK;
 }
 
 // ---- host-buffer transport (app3.py:168-172,189,215,244-250: the reference crosses host <-> device every hop)

@@ -278,6 +278,15 @@ int dn_clip_process(const dn_model* m, const dn_dsp* d, const void* hops_in, int
  * per pipe from 0 (dn_pipe_stream_set_state can restore it), so a replayed launch does not repeat phases and a resumed
  * stream continues the sequence of the uninterrupted one.
  *
+ * Reconfiguring a live pipe: a pipe may change mode while it carries a stream.  dn_pipe_set_head_start, dn_pipe_set_gl_schedule and
+ * dn_pipe_set_split may be called between any two launches, with a hop in flight: a frame carries what it needs in its scratch slot (a chain
+ * parked under one schedule is resumed under the other).  dn_pipe_set_depth, dn_pipe_set_group and dn_pipe_stream_set_state want a drained pipe
+ * (after create, dn_pipe_flush, depth x dn_pipe_stream_flush or dn_pipe_stream_flush_group; the first two refuse a pipe with hops in flight, the
+ * third drops them).  Across every such switch frames, hx, emitted samples and the seed sequence (frame f draws from seed + f) continue bit for
+ * bit as on a pipe that was never reconfigured; a setter that returns an error has changed nothing.  The priming count behind *hops_valid of
+ * dn_pipe_stream_flush_group covers every hop this pipe has taken: single-hop pushes before dn_pipe_set_group count (the setter reads the
+ * control block), as do restored states, so a stream that was primed by single pushes gets H valid hops from its first group.
+ *
  * A pipe holds a reference on its model and plan: dn_model_destroy / dn_dsp_destroy while a pipe still uses them only drop
  * the creator's reference.  dn_pipe_set_model rebinds a pipe to other weights between two launches (launches already
  * enqueued keep reading the old model: keep it alive until they have run).  flags: DN_CONV_BF16 or 0. */
@@ -331,7 +340,8 @@ int dn_pipe_stream_flush_group(dn_pipe* p, void* hop_out, int64_t out_stride, in
  *   DN_GL_WAVE_PER_STREAM  one wavefront per stream, the three columns interleaved inside it, four streams per workgroup: no workgroup
  *                          barrier, the overlap-add in registers, four times the streams in flight -- right for several streams per CU;
  *   DN_GL_AUTO (default)   per stream from 768 streams per pipe on (three per CU of an MI355X: the measured crossover), per column below.
- * Call between launches. */
+ * Call between launches.  A deep pipe and a group pipe run a wavefront per stream whatever is set here: DN_GL_WAVE_PER_COLUMN on either is
+ * DN_ERR_INVALID, and a schedule set before dn_pipe_set_depth / dn_pipe_set_group takes effect again at depth 1 / after dn_pipe_set_group(p, 0). */
 #define DN_GL_AUTO 0
 #define DN_GL_WAVE_PER_COLUMN 1
 #define DN_GL_WAVE_PER_STREAM 2

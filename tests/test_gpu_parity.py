@@ -1531,6 +1531,10 @@ def test_hop_groups_refuse_what_they_do_not_run_and_replay_under_a_graph(dev):
     pipe.set_group(2)
     with pytest.raises(DnError, match="group pipe"):
         pipe.set_depth(2)
+    with pytest.raises(DnError, match="group pipe"):              # (as on a deep pipe: whole chains run a wavefront per stream)
+        pipe.set_gl_schedule(1)
+    pipe.set_gl_schedule(2)
+    pipe.set_gl_schedule(0)
     f = torch.zeros(3, 4, p.n_fft, device=dev)
     with pytest.raises(DnError, match="hops must be"):
         pipe.submit_group(f, dn.init_hx(4), torch.empty_like(f))

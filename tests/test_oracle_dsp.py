@@ -8,6 +8,7 @@ import torch
 
 from conftest import load_golden
 import dsp_cases
+import pipe_cases
 from dsp_cases import WINDOWS, window
 from oracle import dsp_np64, dsp_ref, pipeline_ref
 
@@ -169,6 +170,13 @@ def test_seed_table_of_the_32_iteration_cases_is_what_the_reference_gives(n_fft,
     """dsp_cases.GL32_SEED_K, derived again: the batch it names is the first on which float64 Griffin-Lim itself stays within 1e-4 RMS a stream
     under 1e-7 perturbations of the magnitudes.  Changing magnitudes(), the windows or the reference without the table fails here."""
     assert dsp_cases.gl32_first_well_conditioned_k(n_fft, name) == dsp_cases.GL32_SEED_K[(n_fft, name)]
+
+
+@pytest.mark.parametrize("n_fft", sorted(pipe_cases.SEED_K))
+def test_seed_table_of_the_pipe_switch_cases_is_what_the_reference_gives(n_fft):
+    """pipe_cases.SEED_K, derived again: the batch it names is the first whose float64 stream (20 frames, six Griffin-Lim iterations) moves no
+    stream by more than 1e-4 RMS under 1e-7 perturbations of the signal."""
+    assert pipe_cases.first_well_conditioned_k(n_fft) == pipe_cases.SEED_K[n_fft]
 
 
 def test_real_clip_fixture_is_reproduced_by_the_oracle():
