@@ -30,6 +30,7 @@ SYMBOLS = (
     "dn_sessions_create", "dn_sessions_destroy", "dn_sessions_open", "dn_sessions_close", "dn_sessions_push", "dn_sessions_set_schedule",
     "dn_sessions_get_counters", "dn_sessions_record_bytes", "dn_sessions_export", "dn_sessions_import",
     "dn_clip_workspace_bytes", "dn_clip_process",
+    "dn_stft_phasors", "dn_workspace_bytes_ex", "dn_clip_workspace_bytes_ex",
 )
 
 DN_PEAK_NORMALIZE = 1
@@ -41,7 +42,8 @@ DN_HOST_DEFER = 2
 DN_SPLIT_AUTO, DN_SPLIT_OFF, DN_SPLIT_ON = -1, 0, 1
 DN_SESS_AUTO, DN_SESS_ONE_LAUNCH, DN_SESS_TWO_LAUNCHES = 0, 1, 2
 DN_CLIP_GL_PER_COLUMN, DN_CLIP_GL_PER_STREAM = 2, 4
-ABI_VERSION = 7
+DN_PHASE_FROM_INPUT = 8
+ABI_VERSION = 8
 
 
 class ModelCfg(C.Structure):
@@ -147,6 +149,11 @@ class DnLib:
         L.dn_clip_workspace_bytes.argtypes = [vp, i32, i32]
         L.dn_clip_workspace_bytes.restype = C.c_size_t
         L.dn_clip_process.argtypes = [vp, vp, p, i32, p, p, p, p, i32, p, u64, u64, i32, f32, vp, i32, i32, u32, vp]
+        L.dn_stft_phasors.argtypes = [vp, p, p, i32, u32, vp]
+        L.dn_workspace_bytes_ex.argtypes = [vp, i32, u32]
+        L.dn_workspace_bytes_ex.restype = C.c_size_t
+        L.dn_clip_workspace_bytes_ex.argtypes = [vp, i32, i32, u32]
+        L.dn_clip_workspace_bytes_ex.restype = C.c_size_t
         if L.dn_abi_version() != ABI_VERSION:
             raise ImportError(f"{path}: ABI version {L.dn_abi_version()} != {ABI_VERSION}; rebuild the extension")
 

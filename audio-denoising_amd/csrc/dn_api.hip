@@ -165,6 +165,7 @@ struct dn_pipe {
     dn_dsp* d = nullptr;
     int B = 0, C = 0;
     bool bf16 = false;                        // DN_CONV_BF16: bf16 MFMA conv tiles in the front half
+    bool phase_in = false;                    // DN_PHASE_FROM_INPUT: every frame's chain starts from the unit phasors of its analysis STFT (scratch_init exists from create on)
     dn::PipeCtl* ctl = nullptr;               // device-resident hop counter / pending flag (what makes a captured launch replayable)
     // scratch slots, used round robin by consecutive frames: depth + 1 of them (a frame's slot is read by every segment of its chain)
     int depth = 1, n_slots = 2;                     // hops of one stream in flight (dn_pipe_set_depth)
@@ -719,6 +720,14 @@ int dn_stft_mel_log1p(const dn_dsp* d, const float* frames, float* mel, float* p
     return check_launch("stft_kernel");
 }
 
+int dn_stft_phasors(const dn_dsp* d, const float* frames, float* phasors, int32_t B, uint32_t flags, void* stream) {
+    if (B == 0) return DN_OK;      // empty batch: nothing to do (pointers of empty tensors are null)
+    if (!d || !frames || !phasors) return fail(DN_ERR_INVALID, "dn_stft_phasors: null argument");
+    if (B < 0) return fail(DN_ERR_INVALID, "dn_stft_phasors: negative batch");
+    dn::launch_stft_phasors(d->view, frames, phasors, B, flags, as_stream(stream));
+    return check_launch("stft_phasor_kernel");
+}
+
 int dn_mel_scale(const dn_dsp* d, const float* mag, float* mel, int32_t B, int32_t T, void* stream) {
     if (!d || !mag || !mel) return fail(DN_ERR_INVALID, "dn_mel_scale: null argument");
     if (d->cfg.n_mels <= 0) return fail(DN_ERR_INVALID, "plan was created without mel stages");
@@ -825,13 +834,24 @@ size_t dn_workspace_bytes(const dn_dsp* d, int32_t B) {
     return frame_scratch_bytes(d, B) + (((size_t)B * d->cfg.n_fft * sizeof(float) + 255) & ~size_t(255));
 }
 
+// the phasor rows of input-phase mode (DN_PHASE_FROM_INPUT): 3 K complex values a frame, behind the workspace the entry point had before
+static size_t phasor_bytes(const dn_dsp* d, size_t frames) {
+    return (frames * 3 * ((size_t)d->cfg.n_fft / 2 + 1) * sizeof(float2) + 255) & ~size_t(255);
+}
+
+size_t dn_workspace_bytes_ex(const dn_dsp* d, int32_t B, uint32_t flags) {
+    if (flags & ~(uint32_t)(DN_CONV_BF16 | DN_PHASE_FROM_INPUT)) return 0;
+    const size_t base = dn_workspace_bytes(d, B);
+    return base == 0 || !(flags & DN_PHASE_FROM_INPUT) ? base : base + phasor_bytes(d, (size_t)B);
+}
+
 static int check_hop_args(const char* who, const dn_model* m, const dn_dsp* d, int32_t B, int32_t n_iter, float momentum, uint32_t flags) {
     if (!m || !d) return fail(DN_ERR_INVALID, std::string(who) + ": null handle");
     if (d->cfg.n_mels <= 0 || d->cfg.n_mels % 16) return fail(DN_ERR_INVALID, "n_mels must be a positive multiple of 16");
     if (B < 0 || n_iter < 0) return fail(DN_ERR_INVALID, std::string(who) + ": negative size");
     if (!(momentum >= 0.0f && momentum < 1.0f)) return fail(DN_ERR_INVALID, "momentum must be in [0, 1)");
     if (d->cfg.n_mels / 16 > dn::kMaxC) return fail(DN_ERR_UNSUPPORTED, "n_mels/16 exceeds the cell kernel's limit");
-    if (flags & ~(uint32_t)DN_CONV_BF16) return fail(DN_ERR_INVALID, std::string(who) + ": unknown flag bits");
+    if (flags & ~(uint32_t)(DN_CONV_BF16 | DN_PHASE_FROM_INPUT)) return fail(DN_ERR_INVALID, std::string(who) + ": unknown flag bits");
     return DN_OK;
 }
 
@@ -842,6 +862,7 @@ int dn_process_frame(const dn_model* m, const dn_dsp* d, const float* frames, fl
     if (!frames || !hx || !out || !workspace) return fail(DN_ERR_INVALID, "dn_process_frame: null argument");
     int rc = check_hop_args("dn_process_frame", m, d, B, n_iter, momentum, flags);
     if (rc != DN_OK) return rc;
+    if ((flags & DN_PHASE_FROM_INPUT) && init_angles) return fail(DN_ERR_INVALID, "dn_process_frame: DN_PHASE_FROM_INPUT takes the phases from the input: init_angles must be NULL");
     const int M = d->cfg.n_mels, K = d->cfg.n_fft / 2 + 1, C = M / 16;
     float* ws = static_cast<float*>(workspace);
     BiasSet* bs = nullptr;
@@ -854,6 +875,7 @@ int dn_process_frame(const dn_model* m, const dn_dsp* d, const float* frames, fl
     a.peak = ws + (size_t)B * 6 * M + (size_t)B * 3 * K;
     a.init = init_angles; a.seed = seed; a.sid0 = stream_id0;
     a.n_iter = n_iter; a.mom = momentum / (1.0f + momentum); a.C = C;
+    if (flags & DN_PHASE_FROM_INPUT) a.phas = reinterpret_cast<float*>(static_cast<char*>(workspace) + dn_workspace_bytes(d, B));
     dn::launch_frame(d->view, bs->view, a, B, (flags & DN_CONV_BF16) != 0, as_stream(stream));      // P1-P12, one launch
     return check_launch("frame_kernel");
 }
@@ -866,6 +888,7 @@ int dn_stream_step(const dn_model* m, const dn_dsp* d, const float* hop_in, floa
     if (!hop_in || !ring || !ola || !hx || !hop_out || !workspace) return fail(DN_ERR_INVALID, "dn_stream_step: null argument");
     int rc = check_hop_args("dn_stream_step", m, d, B, n_iter, momentum, flags);
     if (rc != DN_OK) return rc;
+    if ((flags & DN_PHASE_FROM_INPUT) && init_angles) return fail(DN_ERR_INVALID, "dn_stream_step: DN_PHASE_FROM_INPUT takes the phases from the input: init_angles must be NULL");
     const int M = d->cfg.n_mels, K = d->cfg.n_fft / 2 + 1, C = M / 16;
     float* ws = static_cast<float*>(workspace);
     BiasSet* bs = nullptr;
@@ -877,6 +900,7 @@ int dn_stream_step(const dn_model* m, const dn_dsp* d, const float* hop_in, floa
     a.init = init_angles; a.seed = seed; a.sid0 = stream_id0;
     a.n_iter = n_iter; a.mom = momentum / (1.0f + momentum); a.C = C;
     a.hop_in = hop_in; a.ring = ring; a.ola = ola; a.hop_out = hop_out;
+    if (flags & DN_PHASE_FROM_INPUT) a.phas = reinterpret_cast<float*>(static_cast<char*>(workspace) + dn_workspace_bytes(d, B));
     dn::launch_frame(d->view, bs->view, a, B, (flags & DN_CONV_BF16) != 0, as_stream(stream));
     return check_launch("frame_kernel(stream)");
 }
@@ -892,6 +916,12 @@ size_t dn_clip_workspace_bytes(const dn_dsp* d, int32_t B, int32_t N) {
     return ((frames * (clip_row_floats(d) + 6 * (size_t)d->cfg.n_mels + 1) * sizeof(float) + 255) & ~size_t(255)) + 256;
 }
 
+size_t dn_clip_workspace_bytes_ex(const dn_dsp* d, int32_t B, int32_t N, uint32_t flags) {
+    if (flags & ~(uint32_t)(DN_CONV_BF16 | DN_PHASE_FROM_INPUT | DN_CLIP_GL_PER_COLUMN | DN_CLIP_GL_PER_STREAM)) return 0;
+    const size_t base = dn_clip_workspace_bytes(d, B, N);
+    return base == 0 || !(flags & DN_PHASE_FROM_INPUT) ? base : base + phasor_bytes(d, (size_t)B * (size_t)N);
+}
+
 int dn_clip_process(const dn_model* m, const dn_dsp* d, const void* hops_in, int32_t in_s16, float* ring, float* ola, float* hx, void* hops_out,
                     int32_t out_s16, const float* init_angles, uint64_t seed, uint64_t stream_id0, int32_t n_iter, float momentum,
                     void* workspace, int32_t B, int32_t N, uint32_t flags, void* stream) {
@@ -905,6 +935,7 @@ int dn_clip_process(const dn_model* m, const dn_dsp* d, const void* hops_in, int
         return fail(DN_ERR_INVALID, "dn_clip_process: DN_CLIP_GL_PER_COLUMN and DN_CLIP_GL_PER_STREAM exclude each other");
     if ((gl & DN_CLIP_GL_PER_STREAM) && d->cfg.n_fft != 1024)
         return fail(DN_ERR_UNSUPPORTED, "the wavefront-per-stream Griffin-Lim is built for n_fft 1024 (at 1536 the per-lane state of a stream does not fit a wavefront's registers; at 512 the schedule is not built)");
+    if ((flags & DN_PHASE_FROM_INPUT) && init_angles) return fail(DN_ERR_INVALID, "dn_clip_process: DN_PHASE_FROM_INPUT takes the phases from the input: init_angles must be NULL");
     if ((long long)B * N > kClipMaxFrames)
         return fail(DN_ERR_INVALID, "dn_clip_process: B x N exceeds " + std::to_string(kClipMaxFrames) + " frames a call (tile the clip)");
     const int M = d->cfg.n_mels, C = M / 16;
@@ -918,6 +949,7 @@ int dn_clip_process(const dn_model* m, const dn_dsp* d, const void* hops_in, int
     a.frames = (size_t)B * (size_t)N;
     a.fr = static_cast<float*>(workspace); a.fr_stride = clip_row_floats(d);
     a.mel = a.fr + a.frames * a.fr_stride; a.diff = a.mel + a.frames * 3 * M; a.peak = a.diff + a.frames * 3 * M;
+    if (flags & DN_PHASE_FROM_INPUT) a.phas = reinterpret_cast<float*>(static_cast<char*>(workspace) + dn_clip_workspace_bytes(d, B, N));
     a.per_stream = d->cfg.n_fft == 1024 && ((gl & DN_CLIP_GL_PER_STREAM) || (gl == 0 && (long)a.frames >= dn::kClipGlwAutoFrames));
     dn::launch_clip(d->view, bs->view_dev, a, (flags & DN_CONV_BF16) != 0, as_stream(stream));
     return check_launch("dn_clip_process");
@@ -941,6 +973,7 @@ int dn_pipe_create(const dn_model* m, const dn_dsp* d, int32_t B, uint32_t flags
     dn_pipe* p = new dn_pipe();
     p->m = const_cast<dn_model*>(m); p->d = const_cast<dn_dsp*>(d); p->B = B; p->C = d->cfg.n_mels / 16;
     p->bf16 = (flags & DN_CONV_BF16) != 0;
+    p->phase_in = (flags & DN_PHASE_FROM_INPUT) != 0;
     p->m->refs.fetch_add(1);       // the pipe keeps the packed weights and the plan alive (its launches read their device arenas)
     p->d->refs.fetch_add(1);
     rc = build_bias(p->m, p->C, &p->bs);
@@ -952,6 +985,9 @@ int dn_pipe_create(const dn_model* m, const dn_dsp* d, int32_t B, uint32_t flags
     hipError_t e = hipMalloc(reinterpret_cast<void**>(&p->ctl), 256);
     if (e == hipSuccess) e = hipMemset(p->ctl, 0, 256);
     if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&p->scratch), p->n_slots * p->slot_floats * sizeof(float));
+    // an input-phase pipe keeps every frame's phasors in its slot: the init area exists from the start (a captured push allocates nothing), and
+    // dn_pipe_set_depth / dn_pipe_set_group re-allocate it with the slots
+    if (e == hipSuccess && p->phase_in) e = hipMalloc(reinterpret_cast<void**>(&p->scratch_init), p->n_slots * p->init_elems * sizeof(float2));
     if (e != hipSuccess) { dn_pipe_destroy(p); return fail(DN_ERR_HIP, std::string("dn_pipe_create: ") + hipGetErrorString(e)); }
     {
         // Griffin-Lim head start: with at most one stream per CU (MI355X: 256 CUs) a front workgroup has slack at the end of a launch that
@@ -1030,7 +1066,7 @@ int dn_pipe_set_depth(dn_pipe* p, int32_t depth) {
     float2* init = nullptr;         // a deep pipe's front workgroups leave every frame's initial phases in its slot (dn_hop.hip)
     hipError_t e = hipMalloc(reinterpret_cast<void**>(&scratch), n_slots * p->slot_floats * sizeof(float));
     if (e == hipSuccess && depth > 1) e = hipMalloc(reinterpret_cast<void**>(&state), n_slots * p->state_elems * sizeof(float2));
-    if (e == hipSuccess && depth > 1) e = hipMalloc(reinterpret_cast<void**>(&init), n_slots * p->init_elems * sizeof(float2));
+    if (e == hipSuccess && (depth > 1 || p->phase_in)) e = hipMalloc(reinterpret_cast<void**>(&init), n_slots * p->init_elems * sizeof(float2));
     if (e != hipSuccess) {
         if (scratch) (void)hipFree(scratch);
         if (state) (void)hipFree(state);
@@ -1187,6 +1223,7 @@ static int fill_hop_args(dn_pipe* p, dn::HopArgs& a, const float* init_angles, u
                          float momentum) {
     if (n_iter < 0) return fail(DN_ERR_INVALID, "negative n_iter");
     if (!(momentum >= 0.0f && momentum < 1.0f)) return fail(DN_ERR_INVALID, "momentum must be in [0, 1)");
+    if (init_angles && p->phase_in) return fail(DN_ERR_INVALID, "this pipe was created with DN_PHASE_FROM_INPUT: it takes the phases from the input, init_angles must be NULL");
     if (init_angles && !p->scratch_init) {
         int rc = dn_pipe_reserve_parity(p);
         if (rc != DN_OK) return rc;
@@ -1198,6 +1235,7 @@ static int fill_hop_args(dn_pipe* p, dn::HopArgs& a, const float* init_angles, u
     a.n_slots = p->n_slots;
     a.gl_split = p->gl_split;
     a.init_in = init_angles; a.seed = seed; a.sid0 = stream_id0;
+    a.phase_in = p->phase_in ? 1 : 0;
     a.n_iter = n_iter; a.mom = momentum / (1.0f + momentum);
     a.B = p->B; a.C = p->C; a.back_B = p->B;
     // a wavefront per stream (four streams a workgroup) from four streams per CU up; a wavefront per column (the shortest chain) below
@@ -1547,6 +1585,7 @@ struct dn_sessions {
     float* hx = nullptr;
     unsigned long long* counters = nullptr;   // frames [cap] | stream ids [cap] | pushes [cap] (u32)
     float* ws = nullptr;                      // mel [cap][3][M] | residual [cap][3][M] | lin [cap][3][K] | peak [cap] | meta [cap][kSessMeta]
+    float* phas = nullptr;                    // DN_PHASE_FROM_INPUT: phasor rows [cap][3][K] complex of a push (list order), else null
     std::vector<char> open;                   // host bookkeeping: which slots are open
     // the id lists (and the stream ids of an open) on their way to the kernels: kRing entries of a page-locked staging ring, entry k reused only
     // after the event recorded behind the last launch that read it has completed
@@ -1675,6 +1714,7 @@ void dn_sessions_destroy(dn_sessions* s) {
     if (s->hx) (void)hipFree(s->hx);
     if (s->counters) (void)hipFree(s->counters);
     if (s->ws) (void)hipFree(s->ws);
+    if (s->phas) (void)hipFree(s->phas);
     if (s->m) model_release(s->m);
     if (s->d) dsp_release(s->d);
     delete s;
@@ -1705,6 +1745,7 @@ int dn_sessions_create(const dn_model* m, const dn_dsp* d, int32_t capacity, uin
     if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&s->hx), hxb);
     if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&s->counters), 3 * cap * sizeof(unsigned long long));
     if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&s->ws), ws);
+    if (e == hipSuccess && (flags & DN_PHASE_FROM_INPUT)) e = hipMalloc(reinterpret_cast<void**>(&s->phas), phasor_bytes(d, cap));
     if (e == hipSuccess) e = hipHostMalloc(reinterpret_cast<void**>(&s->stage_host), dn_sessions::kRing * s->stage_bytes, 0);
     if (e == hipSuccess) e = hipHostMalloc(reinterpret_cast<void**>(&s->chk_host), cap * sizeof(uint32_t), 0);
     if (e == hipSuccess) e = hipHostGetDevicePointer(reinterpret_cast<void**>(&s->chk_dev), s->chk_host, 0);
@@ -1765,6 +1806,7 @@ int dn_sessions_push(dn_sessions* s, const int32_t* ids, int32_t n, const void* 
     int rc = sess_check_ids(s, "dn_sessions_push", ids, n, true);
     if (rc != DN_OK || n == 0) return rc;
     if (!hop_in || !hop_out) return fail(DN_ERR_INVALID, "dn_sessions_push: null argument");
+    if (init_angles && s->phas) return fail(DN_ERR_INVALID, "dn_sessions_push: this pool was created with DN_PHASE_FROM_INPUT: it takes the phases from the input, init_angles must be NULL");
     rc = check_hop_args("dn_sessions_push", s->m, s->d, n, n_iter, momentum, 0);
     if (rc != DN_OK) return rc;
     hipStream_t st = as_stream(stream);
@@ -1772,10 +1814,11 @@ int dn_sessions_push(dn_sessions* s, const int32_t* ids, int32_t n, const void* 
     rc = sess_stage(s, ids, n, nullptr, st, a, nullptr);
     if (rc != DN_OK) return rc;
     a.hop_in = hop_in; a.in_s16 = in_is_s16 ? 1 : 0; a.hop_out = hop_out; a.out_s16 = out_is_s16 ? 1 : 0;
-    a.init = init_angles; a.seed = seed; a.n_iter = n_iter; a.mom = momentum / (1.0f + momentum);
+    const bool phase_in = s->phas != nullptr;
+    a.init = phase_in ? s->phas : init_angles; a.seed = seed; a.n_iter = n_iter; a.mom = momentum / (1.0f + momentum);
     const bool two = s->d->cfg.n_fft == 1024 && (s->schedule == DN_SESS_TWO_LAUNCHES || (s->schedule == DN_SESS_AUTO && n >= kSessSplitAuto));
-    if (two) dn::launch_sess_split(s->d->view, s->bs->view, a, s->bf16, st);
-    else dn::launch_sess_frame(s->d->view, s->bs->view, a, s->bf16, st);
+    if (two) dn::launch_sess_split(s->d->view, s->bs->view, a, s->bf16, st, phase_in);
+    else dn::launch_sess_frame(s->d->view, s->bs->view, a, s->bf16, st, phase_in);
     rc = check_launch(two ? "sess_front_kernel / sess_chain_kernel" : "sess_frame_kernel");
     if (rc != DN_OK) return rc;
     return sess_staged(s, st);

@@ -62,7 +62,9 @@ void launch_clip_chains_glw(const DspDev& d, const ClipArgs& a, hipStream_t st) 
 void launch_clip_chains_glw(const DspDev& d, const ClipArgs& a, hipStream_t st);          // (dn_clip_glw.hip)
 
 // ---- 1. analysis: workgroup f = b N + i stages frame i of stream b and runs P1-P6 on it
-template <int NFFT>
+// PHIN (DN_PHASE_FROM_INPUT): it also stores the unit phasors of the frame's STFT in the workspace's phasor row f, which launch_clip hands the chains of
+// either layout as their init (two kernel boundaries later).
+template <int NFFT, bool PHIN>
 __global__ __launch_bounds__(kHopPipeThreads) void clip_analysis_kernel(DspDev d, ClipArgs a) {
     constexpr int kNR = NFFT, kHop = NFFT / 2, kLine4 = kNR / 4, kHop4 = kHop / 4;
     static_assert(kLine4 <= 2 * kHopPipeThreads, "two float4 per thread cover the frame");
@@ -92,7 +94,8 @@ __global__ __launch_bounds__(kHopPipeThreads) void clip_analysis_kernel(DspDev d
         reinterpret_cast<float4*>(row)[j4] = v;
     }
     __syncthreads();
-    stft_body<NFFT, false, true, kHopPipeThreads>(smem, d, row, nullptr, a.mel + f * 3 * d.n_mels, a.peak + f, DN_PEAK_NORMALIZE | DN_PRE_WINDOW, 0, tid);   // P1-P6
+    stft_body<NFFT, false, true, kHopPipeThreads, PHIN>(smem, d, row, nullptr, a.mel + f * 3 * d.n_mels, a.peak + f, DN_PEAK_NORMALIZE | DN_PRE_WINDOW, 0, tid,
+                                                        PHIN ? reinterpret_cast<float2*>(a.phas) + f * 3 * Geo<NFFT>::kBins : nullptr);   // P1-P6
 }
 
 // ---- 2. model: workgroup b runs the stream's N forwards back to back (P7), hx in place
@@ -194,14 +197,17 @@ __global__ __launch_bounds__(kClipFoldThreads) void clip_fold_kernel(ClipArgs a)
     }
 }
 
-void launch_clip(const DspDev& d, const CellDev* c_dev, const ClipArgs& a, bool bf16, hipStream_t st) {
+void launch_clip(const DspDev& d, const CellDev* c_dev, const ClipArgs& args, bool bf16, hipStream_t st) {
+    ClipArgs a = args;
+    if (a.phas != nullptr) a.init = a.phas;          // input-phase mode: the chains start from the phasors the analysis stores
     const dim3 frames((unsigned)a.frames), block(kHopPipeThreads);
     auto sized = [&](auto k512, auto k1024, auto k1536, dim3 blk) {
         if (d.n_fft == 512) hipLaunchKernelGGL(k512, frames, blk, 0, st, d, a);
         else if (d.n_fft == 1536) hipLaunchKernelGGL(k1536, frames, blk, 0, st, d, a);
         else hipLaunchKernelGGL(k1024, frames, blk, 0, st, d, a);
     };
-    sized(clip_analysis_kernel<512>, clip_analysis_kernel<1024>, clip_analysis_kernel<1536>, block);
+    if (a.phas != nullptr) sized(clip_analysis_kernel<512, true>, clip_analysis_kernel<1024, true>, clip_analysis_kernel<1536, true>, block);
+    else sized(clip_analysis_kernel<512, false>, clip_analysis_kernel<1024, false>, clip_analysis_kernel<1536, false>, block);
     const int usual = d.n_fft == 1024 ? 5 : 4;
     auto model = [&](auto k) { hipLaunchKernelGGL(k, dim3(a.B), block, 0, st, c_dev, a); };
     if (a.C == usual && usual == 5) { if (bf16) model(clip_model_kernel<true, 5>); else model(clip_model_kernel<false, 5>); }

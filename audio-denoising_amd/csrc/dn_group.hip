@@ -28,7 +28,10 @@ static __device__ unsigned long long g_group_wg[2048][2];
 #define DN_GWG(id) do { } while (0)
 #endif
 
-template <int NFFT, bool STREAM, bool BF16, int CT>
+// PHIN: an input-phase pipe (a.phase_in; DN_PHASE_FROM_INPUT): every fronted hop stores the unit phasors of its STFT in its slot's init area and marks the
+// frame as carrying its phases; its chain, in the next launch, starts from them and draws nothing.  A template parameter and not a run-time branch: the
+// front loop spills when anything in it is hoisted (below), and the default instantiation stays the kernel it was.
+template <int NFFT, bool STREAM, bool BF16, int CT, bool PHIN = false>
 __global__ __launch_bounds__(kHopPipeThreads, 2) void group_kernel(DspDev d, const DspDev* __restrict__ dp, const CellDev* __restrict__ cp, HopArgs a) {
     // n_fft 1024 only.  At 1536 a chain wave needs the state of three columns of 768 complex values: 420 registers.  Built in round 4 as a split group
     // (the chains as a launch of their own, one wave a SIMD, nothing spilled; the front halves as a second launch) and measured SLOWER than the one-hop
@@ -155,7 +158,8 @@ __global__ __launch_bounds__(kHopPipeThreads, 2) void group_kernel(DspDev d, con
             if (s >= a.n_slots) s -= a.n_slots;
             float* slot = a.slots + (size_t)s * a.slot_stride;
             DN_GSTAMP(q, 0);
-            stft_body<NFFT, false, true, kHopPipeThreads>(smem, dz, frames_in, nullptr, slot, slot + sl.peak, DN_PEAK_NORMALIZE | DN_PRE_WINDOW, b, tidz);   // P1-P6
+            stft_body<NFFT, false, true, kHopPipeThreads, PHIN>(smem, dz, frames_in, nullptr, slot, slot + sl.peak, DN_PEAK_NORMALIZE | DN_PRE_WINDOW, b, tidz,
+                                                                PHIN ? a.slot_init + (size_t)s * a.init_stride : nullptr);   // P1-P6
             __syncthreads();
             DN_GSTAMP(q, 1);
             cell_body<kHopPipeThreads / 64, BF16, CT>(smem, cz, slot, a.hx + z, slot + sl.diff, a.hx + z, 3, a.C, b, tidz);                               // P7
@@ -166,7 +170,7 @@ __global__ __launch_bounds__(kHopPipeThreads, 2) void group_kernel(DspDev d, con
             if (tid == 0) {
                 uint32_t* meta = reinterpret_cast<uint32_t*>(slot + sl.meta) + kSlotMeta * b;
                 const uint64_t seed = a.seed + frames + (unsigned long long)q;
-                meta[0] = a.init_in != nullptr ? 1u : 0u;
+                meta[0] = (PHIN || a.init_in != nullptr) ? 1u : 0u;
                 meta[1] = (uint32_t)seed;
                 meta[2] = (uint32_t)(seed >> 32);
                 meta[3] = (uint32_t)a.sid0;
@@ -178,7 +182,7 @@ __global__ __launch_bounds__(kHopPipeThreads, 2) void group_kernel(DspDev d, con
                 meta[8] = (uint32_t)dst;
                 meta[9] = (uint32_t)(dst >> 32);
             }
-            if (a.init_in != nullptr) {
+            if (!PHIN && a.init_in != nullptr) {
                 const float2* src = reinterpret_cast<const float2*>(a.init_in + (size_t)h * (size_t)a.init_in_stride) + b * 3 * kBins;
                 float2* dst = a.slot_init + (size_t)s * a.init_stride + b * 3 * kBins;
                 for (int i = tid; i < 3 * kBins; i += kHopPipeThreads) dst[i] = src[i];
@@ -209,13 +213,15 @@ void launch_group(const DspDev& d, const CellDev& c, const HopArgs& a, bool bf16
     const dim3 grid(a.back_blocks + a.front_B), block(kHopPipeThreads);
     const bool stream = a.ola != nullptr, usual = a.C == 5;
     auto go = [&](auto k) { hipLaunchKernelGGL(k, grid, block, 0, st, d, a.d_dev, a.c_dev, a); };
-    if (stream) {
-        if (usual) { if (bf16) go(group_kernel<1024, true, true, 5>); else go(group_kernel<1024, true, false, 5>); }
-        else { if (bf16) go(group_kernel<1024, true, true, 0>); else go(group_kernel<1024, true, false, 0>); }
-    } else {
-        if (usual) { if (bf16) go(group_kernel<1024, false, true, 5>); else go(group_kernel<1024, false, false, 5>); }
-        else { if (bf16) go(group_kernel<1024, false, true, 0>); else go(group_kernel<1024, false, false, 0>); }
-    }
+    auto pick = [&](auto stream_c, auto phin_c) {
+        constexpr bool S = decltype(stream_c)::value, P = decltype(phin_c)::value;
+        if (usual) { if (bf16) go(group_kernel<1024, S, true, 5, P>); else go(group_kernel<1024, S, false, 5, P>); }
+        else { if (bf16) go(group_kernel<1024, S, true, 0, P>); else go(group_kernel<1024, S, false, 0, P>); }
+    };
+    using T = std::true_type; using F = std::false_type;
+    const bool phin = a.phase_in && a.front_B > 0;          // (a flush runs no analysis: the default instantiation)
+    if (stream) { if (phin) pick(T{}, T{}); else pick(T{}, F{}); }
+    else { if (phin) pick(F{}, T{}); else pick(F{}, F{}); }
 }
 
 }  // namespace dn

@@ -68,7 +68,11 @@ static __device__ unsigned int g_hop_blk_hw[2048];          // where every workg
 //      workgroups (the low block ids) run first and its front workgroups after them anyway -- two phases, not a mix -- and a front workgroup
 //      compiled beside the chain inherits the chain's 243 registers: two workgroups a CU.  On its own the front half is capped at
 //      kFrontPerCu workgroups a CU (its phases end at workgroup barriers and wait on memory: more of them in flight is what it wants).
-template <int NFFT, bool STREAM, bool BF16, int CT, bool GLW, bool FRONT = false>
+// PHIN: an input-phase pipe (a.phase_in; DN_PHASE_FROM_INPUT): the front half stores the unit phasors of its STFT in the slot's init area and marks the
+//      frame as carrying its phases; nothing is drawn, by the spare wave or by the chain.  A template parameter: the default instantiation is unchanged.
+//      The head start reads the slot back in the same workgroup: wave w / lane l loads the bins wave w / lane l stored (stft_body; every n_fft), so
+//      program order covers it, with workgroup barriers between besides.  Every other reader (the chains of a later launch) is behind a kernel boundary.
+template <int NFFT, bool STREAM, bool BF16, int CT, bool GLW, bool FRONT = false, bool PHIN = false>
 __global__ __launch_bounds__(kHopPipeThreads, FRONT ? kFrontPerCu : (NFFT == 1536 || GLW) ? 2 : 1) void hop_kernel(DspDev d, CellDev cd, HopArgs a) {
     constexpr int kNR = NFFT, kBins = Geo<NFFT>::kBins;
     __shared__ __attribute__((aligned(16))) char smem[FRONT ? front_smem<NFFT>() : hop_smem<NFFT>()];
@@ -203,13 +207,14 @@ __global__ __launch_bounds__(kHopPipeThreads, FRONT ? kFrontPerCu : (NFFT == 153
             const int s = (int)slot_next;
             float* slot = a.slots + (size_t)s * a.slot_stride;
             float2* slot_init = a.slot_init + (size_t)s * a.init_stride;
-            stft_body<NFFT, false, true, kHopPipeThreads>(smem, d, frames_in, nullptr, slot, slot + sl.peak, DN_PEAK_NORMALIZE | DN_PRE_WINDOW, b, tid);   // P1-P6
+            stft_body<NFFT, false, true, kHopPipeThreads, PHIN>(smem, d, frames_in, nullptr, slot, slot + sl.peak, DN_PEAK_NORMALIZE | DN_PRE_WINDOW, b, tid,
+                                                                slot_init);   // P1-P6
             const int split = FRONT ? 0 : min(a.gl_split, a.n_iter);        // (a split hop has no head start)
             // (measured: n_fft 1536, 13 bins a lane: 106 -> 100 us per batch-256 hop; n_fft 1024, 9 bins a lane: 54.7 -> 55.2 us -- the draw's 12 KB
             // a stream through HBM cost more than the multiplies it moved off the chain, so only the long transform uses it)
             // A deep pipe (a.depth > 1: the chain runs as segments, one wavefront per stream) draws here too, at either transform length: there the
             // draw is 27 Philox blocks a lane (~12 k cycles) on the first segment's wave, which then has to get an iteration less than the others.
-            const bool draw = a.init_in == nullptr && (NFFT == 1536 ? split > 0 : a.depth > 1);
+            const bool draw = !PHIN && a.init_in == nullptr && (NFFT == 1536 ? split > 0 : a.depth > 1);
             if (draw && tid >= kHopThreads) {
                 // The fourth wave has no column to transform and would wait here: it draws the random initial phases the head start
                 // below begins with (the same Philox blocks, so the same bits) into the slot.  A block is ten rounds of quarter-rate integer
@@ -235,7 +240,7 @@ __global__ __launch_bounds__(kHopPipeThreads, FRONT ? kFrontPerCu : (NFFT == 153
             if (tid == 0) {
                 uint32_t* meta = reinterpret_cast<uint32_t*>(slot + sl.meta) + kSlotMeta * b;
                 const uint64_t seed = a.seed + frames;
-                meta[0] = (a.init_in != nullptr || (draw && a.depth > 1)) ? 1u : 0u;       // the frame's phases are in the slot
+                meta[0] = (PHIN || a.init_in != nullptr || (draw && a.depth > 1)) ? 1u : 0u;       // the frame's phases are in the slot
                 meta[1] = (uint32_t)seed;
                 meta[2] = (uint32_t)(seed >> 32);
                 meta[3] = (uint32_t)a.sid0;
@@ -247,7 +252,7 @@ __global__ __launch_bounds__(kHopPipeThreads, FRONT ? kFrontPerCu : (NFFT == 153
                 meta[8] = (uint32_t)dst;
                 meta[9] = (uint32_t)(dst >> 32);
             }
-            if (a.init_in != nullptr) {
+            if (!PHIN && a.init_in != nullptr) {
                 const float2* src = reinterpret_cast<const float2*>(a.init_in) + b * 3 * kBins;
                 float2* dst = slot_init + b * 3 * kBins;
                 for (int i = tid; i < 3 * kBins; i += kHopPipeThreads) dst[i] = src[i];
@@ -258,7 +263,7 @@ __global__ __launch_bounds__(kHopPipeThreads, FRONT ? kFrontPerCu : (NFFT == 153
                 if (tid >= kHopThreads) return;        // the chain is three waves wide
                 __builtin_amdgcn_s_setprio(DN_HS_PRIO); // below the pending hop's chain (3): that one ends the launch
                 gl_body<NFFT, false, false, NFFT == 1536>(smem, d, slot + sl.lin, nullptr,
-                                            draw ? reinterpret_cast<const v2f*>(slot_init) : reinterpret_cast<const v2f*>(a.init_in), a.seed + frames, a.sid0,
+                                            (PHIN || draw) ? reinterpret_cast<const v2f*>(slot_init) : reinterpret_cast<const v2f*>(a.init_in), a.seed + frames, a.sid0,
                                             nullptr, nullptr, a.n_iter, a.mom, b, tid, nullptr, nullptr, 0, 0, split,
                                             reinterpret_cast<v2f*>(a.gl_state + (size_t)s * a.state_stride));
                 __builtin_amdgcn_s_setprio(0);
@@ -311,31 +316,37 @@ __global__ __launch_bounds__(kHopPipeThreads, FRONT ? kFrontPerCu : (NFFT == 153
     }
 }
 
-template <int NFFT, bool STREAM, bool GLW>
-static void launch_hop_n(const DspDev& d, const CellDev& c, const HopArgs& a, bool bf16, hipStream_t st) {
+template <int NFFT, bool STREAM, bool GLW, bool PHIN>
+static void launch_hop_p(const DspDev& d, const CellDev& c, const HopArgs& a, bool bf16, hipStream_t st) {
     const dim3 block(kHopPipeThreads);
     constexpr int kUsualC = NFFT == 1024 ? 5 : 4;
     if constexpr (GLW) {
         if (a.front_only) {             // the second launch of a split hop: front workgroups alone, under their own register budget
             const dim3 fgrid(a.front_B);
             if (a.C == kUsualC) {
-                if (bf16) hipLaunchKernelGGL((hop_kernel<NFFT, STREAM, true, kUsualC, true, true>), fgrid, block, 0, st, d, c, a);
-                else hipLaunchKernelGGL((hop_kernel<NFFT, STREAM, false, kUsualC, true, true>), fgrid, block, 0, st, d, c, a);
+                if (bf16) hipLaunchKernelGGL((hop_kernel<NFFT, STREAM, true, kUsualC, true, true, PHIN>), fgrid, block, 0, st, d, c, a);
+                else hipLaunchKernelGGL((hop_kernel<NFFT, STREAM, false, kUsualC, true, true, PHIN>), fgrid, block, 0, st, d, c, a);
             } else {
-                if (bf16) hipLaunchKernelGGL((hop_kernel<NFFT, STREAM, true, 0, true, true>), fgrid, block, 0, st, d, c, a);
-                else hipLaunchKernelGGL((hop_kernel<NFFT, STREAM, false, 0, true, true>), fgrid, block, 0, st, d, c, a);
+                if (bf16) hipLaunchKernelGGL((hop_kernel<NFFT, STREAM, true, 0, true, true, PHIN>), fgrid, block, 0, st, d, c, a);
+                else hipLaunchKernelGGL((hop_kernel<NFFT, STREAM, false, 0, true, true, PHIN>), fgrid, block, 0, st, d, c, a);
             }
             return;
         }
     }
     const dim3 grid(a.back_blocks + a.front_B);
     if (a.C == kUsualC) {
-        if (bf16) hipLaunchKernelGGL((hop_kernel<NFFT, STREAM, true, kUsualC, GLW>), grid, block, 0, st, d, c, a);
-        else hipLaunchKernelGGL((hop_kernel<NFFT, STREAM, false, kUsualC, GLW>), grid, block, 0, st, d, c, a);
+        if (bf16) hipLaunchKernelGGL((hop_kernel<NFFT, STREAM, true, kUsualC, GLW, false, PHIN>), grid, block, 0, st, d, c, a);
+        else hipLaunchKernelGGL((hop_kernel<NFFT, STREAM, false, kUsualC, GLW, false, PHIN>), grid, block, 0, st, d, c, a);
     } else {
-        if (bf16) hipLaunchKernelGGL((hop_kernel<NFFT, STREAM, true, 0, GLW>), grid, block, 0, st, d, c, a);
-        else hipLaunchKernelGGL((hop_kernel<NFFT, STREAM, false, 0, GLW>), grid, block, 0, st, d, c, a);
+        if (bf16) hipLaunchKernelGGL((hop_kernel<NFFT, STREAM, true, 0, GLW, false, PHIN>), grid, block, 0, st, d, c, a);
+        else hipLaunchKernelGGL((hop_kernel<NFFT, STREAM, false, 0, GLW, false, PHIN>), grid, block, 0, st, d, c, a);
     }
+}
+// (a launch without front workgroups -- a flush, the chains' launch of a split hop -- runs no analysis: it takes the default instantiation)
+template <int NFFT, bool STREAM, bool GLW>
+static void launch_hop_n(const DspDev& d, const CellDev& c, const HopArgs& a, bool bf16, hipStream_t st) {
+    if (a.phase_in && a.front_B > 0) launch_hop_p<NFFT, STREAM, GLW, true>(d, c, a, bf16, st);
+    else launch_hop_p<NFFT, STREAM, GLW, false>(d, c, a, bf16, st);
 }
 
 #if !defined(DN_HOP_TU_SIDE)
@@ -411,7 +422,10 @@ void launch_ctl_set(PipeCtl* ctl, unsigned long long pushes, unsigned long long 
 
 // ---- the unpipelined hop: P1-P12 of one stream in one workgroup, one launch per hop (zero added latency).  Four wavefronts for the
 // front half (the conv phases split four ways), three for the Griffin-Lim chain behind it (the fourth exits).
-template <int NFFT, bool STREAM, bool BF16, int CT>
+// PHIN (DN_PHASE_FROM_INPUT; a.phas != null): the analysis also stores the unit phasors of its STFT in the workspace and the chain starts from them.
+// A template parameter, so the default instantiation is the kernel it was.  Wave w / lane l of the chain loads the bins wave w / lane l of the
+// analysis stored (stft_body; n_fft 512, 1024 and 1536 alike), so program order covers the hand-over -- and two workgroup barriers lie between.
+template <int NFFT, bool STREAM, bool BF16, int CT, bool PHIN = false>
 __global__ __launch_bounds__(kHopPipeThreads, NFFT == 1536 ? 2 : 1) void frame_kernel(DspDev d, CellDev cd, FrameArgs a) {
     __shared__ __attribute__((aligned(16))) char smem[hop_smem<NFFT>()];
     const int tid = threadIdx.x;
@@ -421,29 +435,36 @@ __global__ __launch_bounds__(kHopPipeThreads, NFFT == 1536 ? 2 : 1) void frame_k
         ring_shift<NFFT, kHopPipeThreads>(a.ring, a.hop_in, 0, b, tid);
         frames_in = a.ring;
     }
-    stft_body<NFFT, false, true, kHopPipeThreads>(smem, d, frames_in, nullptr, a.mel, a.peak, DN_PEAK_NORMALIZE | DN_PRE_WINDOW, b, tid);   // P1-P6
+    stft_body<NFFT, false, true, kHopPipeThreads, PHIN>(smem, d, frames_in, nullptr, a.mel, a.peak, DN_PEAK_NORMALIZE | DN_PRE_WINDOW, b, tid,
+                                                        reinterpret_cast<float2*>(a.phas));   // P1-P6
     __syncthreads();
     cell_body<kHopPipeThreads / 64, BF16, CT>(smem, cd, a.mel, a.hx, a.diff, a.hx, 3, a.C, b, tid);                                      // P7
     __syncthreads();
     if (tid >= kHopThreads) return;
+    const v2f* init = reinterpret_cast<const v2f*>(PHIN ? a.phas : a.init);
     // P8-P12: the inverse-mel contraction is the Griffin-Lim prologue (the linear magnitudes stay in LDS)
     if (!STREAM)
-        gl_body<NFFT, true, false>(smem, d, a.mel, a.diff, reinterpret_cast<const v2f*>(a.init), a.seed, a.sid0, a.peak, a.out, a.n_iter, a.mom, b, tid);
+        gl_body<NFFT, true, false>(smem, d, a.mel, a.diff, init, a.seed, a.sid0, a.peak, a.out, a.n_iter, a.mom, b, tid);
     else
-        gl_body<NFFT, true, true>(smem, d, a.mel, a.diff, reinterpret_cast<const v2f*>(a.init), a.seed, a.sid0, a.peak, nullptr, a.n_iter, a.mom, b, tid,
+        gl_body<NFFT, true, true>(smem, d, a.mel, a.diff, init, a.seed, a.sid0, a.peak, nullptr, a.n_iter, a.mom, b, tid,
                                   a.ola, a.hop_out, 0);
 }
 
-template <int NFFT, bool STREAM>
-static void launch_frame_n(const DspDev& d, const CellDev& c, const FrameArgs& a, int B, bool bf16, hipStream_t st) {
+template <int NFFT, bool STREAM, bool PHIN>
+static void launch_frame_p(const DspDev& d, const CellDev& c, const FrameArgs& a, int B, bool bf16, hipStream_t st) {
     constexpr int kUsualC = NFFT == 1024 ? 5 : 4;
     if (a.C == kUsualC) {
-        if (bf16) hipLaunchKernelGGL((frame_kernel<NFFT, STREAM, true, kUsualC>), dim3(B), dim3(kHopPipeThreads), 0, st, d, c, a);
-        else hipLaunchKernelGGL((frame_kernel<NFFT, STREAM, false, kUsualC>), dim3(B), dim3(kHopPipeThreads), 0, st, d, c, a);
+        if (bf16) hipLaunchKernelGGL((frame_kernel<NFFT, STREAM, true, kUsualC, PHIN>), dim3(B), dim3(kHopPipeThreads), 0, st, d, c, a);
+        else hipLaunchKernelGGL((frame_kernel<NFFT, STREAM, false, kUsualC, PHIN>), dim3(B), dim3(kHopPipeThreads), 0, st, d, c, a);
     } else {
-        if (bf16) hipLaunchKernelGGL((frame_kernel<NFFT, STREAM, true, 0>), dim3(B), dim3(kHopPipeThreads), 0, st, d, c, a);
-        else hipLaunchKernelGGL((frame_kernel<NFFT, STREAM, false, 0>), dim3(B), dim3(kHopPipeThreads), 0, st, d, c, a);
+        if (bf16) hipLaunchKernelGGL((frame_kernel<NFFT, STREAM, true, 0, PHIN>), dim3(B), dim3(kHopPipeThreads), 0, st, d, c, a);
+        else hipLaunchKernelGGL((frame_kernel<NFFT, STREAM, false, 0, PHIN>), dim3(B), dim3(kHopPipeThreads), 0, st, d, c, a);
     }
+}
+template <int NFFT, bool STREAM>
+static void launch_frame_n(const DspDev& d, const CellDev& c, const FrameArgs& a, int B, bool bf16, hipStream_t st) {
+    if (a.phas != nullptr) launch_frame_p<NFFT, STREAM, true>(d, c, a, B, bf16, st);
+    else launch_frame_p<NFFT, STREAM, false>(d, c, a, B, bf16, st);
 }
 
 #if !defined(DN_HOP_TU_SIDE)

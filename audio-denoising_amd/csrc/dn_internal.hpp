@@ -114,6 +114,7 @@ constexpr int kArenaSlack = 8192; // zero bytes behind every device arena: kerne
 
 void launch_stft(const DspDev& d, const float* frames, float* spec, float* mel, float* peak, int B, uint32_t flags,
                  hipStream_t st);
+void launch_stft_phasors(const DspDev& d, const float* frames, float* phas, int B, uint32_t flags, hipStream_t st);
 void launch_mel(const DspDev& d, const float* mag, float* mel, int rows, hipStream_t st);
 void launch_invmel(const DspDev& d, const float* x, const float* diff, float* lin, int rows, hipStream_t st);
 void launch_griffinlim(const DspDev& d, const float* mag, const float* init, uint64_t seed, uint64_t sid0,
@@ -184,6 +185,9 @@ struct HopArgs {
     int group_hops, group_out, filler_first, n_mels;
     const DspDev* d_dev; const CellDev* c_dev;          // device copies of the plan's and the model's views (group_kernel reads them where it needs them)
     long long frames_stride, out_stride, init_in_stride, hop_in_stride, hop_out_stride;
+    // input-phase pipe (DN_PHASE_FROM_INPUT): the front half stores the unit phasors of its STFT in the slot's init area, nothing is drawn.  (The last
+    // member: the kernel-argument offsets of everything above are what they were, so the default instantiations compile to the code they were.)
+    int phase_in;
 };
 void launch_host_copy(const uint4* src, uint4* dst, unsigned int n16, unsigned long long* done, unsigned long long value, hipStream_t st);
 void launch_hop(const DspDev& d, const CellDev& c, const HopArgs& a, bool bf16, hipStream_t st);
@@ -197,6 +201,7 @@ struct FrameArgs {
     const float* init; uint64_t seed, sid0;
     int n_iter; float mom; int C;
     const float* hop_in; float* ring; float* ola; float* hop_out;    // dn_stream_step (ring != null)
+    float* phas;             // DN_PHASE_FROM_INPUT: workspace rows [B][3][K] complex for the unit phasors of the analysis STFT (the chain's initial phases), else null
 };
 void launch_frame(const DspDev& d, const CellDev& c, const FrameArgs& a, int B, bool bf16, hipStream_t st);
 // One hop for n listed slots of a session pool (dn_sessions.hip).  Slot-indexed: ring, ola, hx and the counters; row-indexed (list order): hop_in,
@@ -209,12 +214,14 @@ struct SessArgs {
     unsigned int* pushes;                                       // [cap] pushes since the open, counted up to `prime`
     int prime;                                                  // n_fft / hop - 1: pushes that only fill the ring
     const void* hop_in; int in_s16; void* hop_out; int out_s16; // [n][hop] float32 or int16
-    const float* init;                                          // [n][3][K] complex initial phases, or null = device RNG
+    const float* init;                                          // [n][3][K] complex initial phases, or null = device RNG; an input-phase pool (phase_in of the
+                                                                // launchers): its phasor rows [cap][3][K] complex in list order, which the analysis WRITES
     float* mel; float* diff; float* lin; float* peak; uint32_t* meta;   // workspace rows [cap][3][M], [cap][3][M], [cap][3][K], [cap], [cap][kSessMeta]
     uint64_t seed; int n_iter; float mom; int C;
 };
-void launch_sess_frame(const DspDev& d, const CellDev& c, const SessArgs& a, bool bf16, hipStream_t st);
-void launch_sess_split(const DspDev& d, const CellDev& c, const SessArgs& a, bool bf16, hipStream_t st);     // n_fft 1024
+// (phase_in is an argument of the launchers and not a member: SessArgs, and with it the kernels' argument layout, stays what it was)
+void launch_sess_frame(const DspDev& d, const CellDev& c, const SessArgs& a, bool bf16, hipStream_t st, bool phase_in = false);
+void launch_sess_split(const DspDev& d, const CellDev& c, const SessArgs& a, bool bf16, hipStream_t st, bool phase_in = false);     // n_fft 1024
 void launch_sess_open(const SessArgs& a, const uint64_t* sids_in, int n_fft, hipStream_t st);
 // Session records (dn_sessions_export / dn_sessions_import; layout: include/dn_denoise.h).  Record i of a call is records + i * stride and
 // belongs to slot ids[i].
@@ -243,6 +250,7 @@ struct ClipArgs {
     float* fr; size_t fr_stride;                                // workspace: frame rows [B N][fr_stride]
     float* mel; float* diff; float* peak;                       //            [B N][3][M], [B N][3][M], [B N]
     int per_stream;                                             // chains a wavefront per frame (n_fft 1024) instead of a wavefront per column
+    float* phas;                                                // DN_PHASE_FROM_INPUT: workspace rows [B N][3][K] complex, written by the analysis, the chains' init; else null
 };
 void launch_clip(const DspDev& d, const CellDev* c_dev, const ClipArgs& a, bool bf16, hipStream_t st);
 void launch_cell_bf16(const CellDev& c, const float* x, const float* hx_in, float* out, float* hx_out, int B, int T,

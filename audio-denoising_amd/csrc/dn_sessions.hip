@@ -41,7 +41,9 @@ __device__ __forceinline__ void sess_zero_row(void* out, int s16, int hop, int t
 }
 
 // ---- one launch: workgroup i runs the whole hop of slot ids[i] (frame_kernel with one level of indirection)
-template <int NFFT, bool BF16, int CT>
+// PHIN (an input-phase pool: a.init is its phasor rows): as frame_kernel's -- the analysis stores the unit phasors of its STFT in row i and the chain starts
+// from them; wave w / lane l reads back what wave w / lane l stored (every n_fft), behind two workgroup barriers.
+template <int NFFT, bool BF16, int CT, bool PHIN = false>
 __global__ __launch_bounds__(kHopPipeThreads, NFFT == 1536 ? 2 : 1) void sess_frame_kernel(DspDev d, CellDev cd, SessArgs a) {
     constexpr int kNR = NFFT, kHop = NFFT / 2, kBins = Geo<NFFT>::kBins;
     __shared__ __attribute__((aligned(16))) char smem[hop_smem<NFFT>()];
@@ -65,34 +67,41 @@ __global__ __launch_bounds__(kHopPipeThreads, NFFT == 1536 ? 2 : 1) void sess_fr
     float* diff = a.diff + i * 3 * M;
     float* peak = a.peak + i;
     float* hx = a.hx + s * kHidden * a.C;
-    stft_body<NFFT, false, true, kHopPipeThreads>(smem, d, ring, nullptr, mel, peak, DN_PEAK_NORMALIZE | DN_PRE_WINDOW, 0, tid);   // P1-P6
+    float2* phas = PHIN ? reinterpret_cast<float2*>(const_cast<float*>(a.init)) + i * 3 * kBins : nullptr;
+    stft_body<NFFT, false, true, kHopPipeThreads, PHIN>(smem, d, ring, nullptr, mel, peak, DN_PEAK_NORMALIZE | DN_PRE_WINDOW, 0, tid, phas);   // P1-P6
     __syncthreads();
     cell_body<kHopPipeThreads / 64, BF16, CT>(smem, cd, mel, hx, diff, hx, 3, a.C, 0, tid);                                      // P7
     __syncthreads();
     if (tid >= kHopThreads) return;
-    const v2f* init = a.init != nullptr ? reinterpret_cast<const v2f*>(a.init) + i * 3 * kBins : nullptr;
+    const v2f* init = PHIN ? reinterpret_cast<const v2f*>(phas) : a.init != nullptr ? reinterpret_cast<const v2f*>(a.init) + i * 3 * kBins : nullptr;
     // P8-P12: the slot's f-th frame draws from (seed + f, the slot's stream id)
     gl_body<NFFT, true, true>(smem, d, mel, diff, init, a.seed + f, sid, peak, nullptr, a.n_iter, a.mom, 0, tid, a.ola + s * kNR, out, a.out_s16);
     if (tid == 0) a.frames[s] = f + 1;
 }
 
-template <int NFFT>
-static void launch_sess_frame_n(const DspDev& d, const CellDev& c, const SessArgs& a, bool bf16, hipStream_t st) {
+template <int NFFT, bool PHIN>
+static void launch_sess_frame_p(const DspDev& d, const CellDev& c, const SessArgs& a, bool bf16, hipStream_t st) {
     constexpr int kUsualC = NFFT == 1024 ? 5 : 4;
     const dim3 grid(a.n), block(kHopPipeThreads);
     if (a.C == kUsualC) {
-        if (bf16) hipLaunchKernelGGL((sess_frame_kernel<NFFT, true, kUsualC>), grid, block, 0, st, d, c, a);
-        else hipLaunchKernelGGL((sess_frame_kernel<NFFT, false, kUsualC>), grid, block, 0, st, d, c, a);
+        if (bf16) hipLaunchKernelGGL((sess_frame_kernel<NFFT, true, kUsualC, PHIN>), grid, block, 0, st, d, c, a);
+        else hipLaunchKernelGGL((sess_frame_kernel<NFFT, false, kUsualC, PHIN>), grid, block, 0, st, d, c, a);
     } else {
-        if (bf16) hipLaunchKernelGGL((sess_frame_kernel<NFFT, true, 0>), grid, block, 0, st, d, c, a);
-        else hipLaunchKernelGGL((sess_frame_kernel<NFFT, false, 0>), grid, block, 0, st, d, c, a);
+        if (bf16) hipLaunchKernelGGL((sess_frame_kernel<NFFT, true, 0, PHIN>), grid, block, 0, st, d, c, a);
+        else hipLaunchKernelGGL((sess_frame_kernel<NFFT, false, 0, PHIN>), grid, block, 0, st, d, c, a);
     }
+}
+template <int NFFT>
+static void launch_sess_frame_n(const DspDev& d, const CellDev& c, const SessArgs& a, bool bf16, hipStream_t st, bool phase_in) {
+    if (phase_in) launch_sess_frame_p<NFFT, true>(d, c, a, bf16, st);
+    else launch_sess_frame_p<NFFT, false>(d, c, a, bf16, st);
 }
 
 #if defined(DN_SESS_TU_GLW)
 // ---- two launches, n_fft 1024.  First: workgroup i runs P1-P10 of slot ids[i] into workspace row i and leaves the frame's seed in meta row i
-// (0 in word 0: a priming push, no chain).
-template <bool BF16, int CT>
+// (0 in word 0: a priming push, no chain).  PHIN (an input-phase pool): it also stores the unit phasors of the row's STFT in phasor row i, which the chain
+// launch takes as its init (a kernel boundary lies between).
+template <bool BF16, int CT, bool PHIN = false>
 __global__ __launch_bounds__(kHopPipeThreads, kFrontPerCu) void sess_front_kernel(DspDev d, CellDev cd, SessArgs a) {
     constexpr int kNR = 1024, kHop = 512, kBins = Geo<1024>::kBins;
     __shared__ __attribute__((aligned(16))) char smem[front_smem<1024>()];
@@ -113,7 +122,8 @@ __global__ __launch_bounds__(kHopPipeThreads, kFrontPerCu) void sess_front_kerne
     float* mel = a.mel + i * 3 * M;
     float* diff = a.diff + i * 3 * M;
     float* hx = a.hx + s * kHidden * a.C;
-    stft_body<kNR, false, true, kHopPipeThreads>(smem, d, ring, nullptr, mel, a.peak + i, DN_PEAK_NORMALIZE | DN_PRE_WINDOW, 0, tid);   // P1-P6
+    stft_body<kNR, false, true, kHopPipeThreads, PHIN>(smem, d, ring, nullptr, mel, a.peak + i, DN_PEAK_NORMALIZE | DN_PRE_WINDOW, 0, tid,
+                                                       PHIN ? reinterpret_cast<float2*>(const_cast<float*>(a.init)) + i * 3 * kBins : nullptr);   // P1-P6
     __syncthreads();
     cell_body<kHopPipeThreads / 64, BF16, CT, false>(smem, cd, mel, hx, diff, hx, 3, a.C, 0, tid);                                   // P7
     __syncthreads();
@@ -149,33 +159,39 @@ __global__ __launch_bounds__(kHopPipeThreads, 2) void sess_chain_kernel(DspDev d
                                a.ola + s * kNR, sess_row(a.hop_out, a.out_s16, i, kHop), a.out_s16, 0, -1, kGlwFresh, nullptr, tid);
 }
 
-void launch_sess_split(const DspDev& d, const CellDev& c, const SessArgs& a, bool bf16, hipStream_t st) {
+template <bool PHIN>
+static void launch_sess_front(const DspDev& d, const CellDev& c, const SessArgs& a, bool bf16, hipStream_t st) {
     const dim3 block(kHopPipeThreads);
     if (a.C == 5) {
-        if (bf16) hipLaunchKernelGGL((sess_front_kernel<true, 5>), dim3(a.n), block, 0, st, d, c, a);
-        else hipLaunchKernelGGL((sess_front_kernel<false, 5>), dim3(a.n), block, 0, st, d, c, a);
+        if (bf16) hipLaunchKernelGGL((sess_front_kernel<true, 5, PHIN>), dim3(a.n), block, 0, st, d, c, a);
+        else hipLaunchKernelGGL((sess_front_kernel<false, 5, PHIN>), dim3(a.n), block, 0, st, d, c, a);
     } else {
-        if (bf16) hipLaunchKernelGGL((sess_front_kernel<true, 0>), dim3(a.n), block, 0, st, d, c, a);
-        else hipLaunchKernelGGL((sess_front_kernel<false, 0>), dim3(a.n), block, 0, st, d, c, a);
+        if (bf16) hipLaunchKernelGGL((sess_front_kernel<true, 0, PHIN>), dim3(a.n), block, 0, st, d, c, a);
+        else hipLaunchKernelGGL((sess_front_kernel<false, 0, PHIN>), dim3(a.n), block, 0, st, d, c, a);
     }
-    hipLaunchKernelGGL(sess_chain_kernel, dim3((a.n + kGlwWaves - 1) / kGlwWaves), block, 0, st, d, a);
+}
+void launch_sess_split(const DspDev& d, const CellDev& c, const SessArgs& a, bool bf16, hipStream_t st, bool phase_in) {
+    // (input-phase pool: a.init is the phasor rows; the front halves store them and the chains start from them as from injected phases)
+    if (phase_in) launch_sess_front<true>(d, c, a, bf16, st);
+    else launch_sess_front<false>(d, c, a, bf16, st);
+    hipLaunchKernelGGL(sess_chain_kernel, dim3((a.n + kGlwWaves - 1) / kGlwWaves), dim3(kHopPipeThreads), 0, st, d, a);
 }
 #elif defined(DN_SESS_TU_1536)
-void launch_sess_frame_1536(const DspDev& d, const CellDev& c, const SessArgs& a, bool bf16, hipStream_t st) {
-    launch_sess_frame_n<1536>(d, c, a, bf16, st);
+void launch_sess_frame_1536(const DspDev& d, const CellDev& c, const SessArgs& a, bool bf16, hipStream_t st, bool phase_in) {
+    launch_sess_frame_n<1536>(d, c, a, bf16, st, phase_in);
 }
 #elif defined(DN_SESS_TU_512)
-void launch_sess_frame_512(const DspDev& d, const CellDev& c, const SessArgs& a, bool bf16, hipStream_t st) {
-    launch_sess_frame_n<512>(d, c, a, bf16, st);
+void launch_sess_frame_512(const DspDev& d, const CellDev& c, const SessArgs& a, bool bf16, hipStream_t st, bool phase_in) {
+    launch_sess_frame_n<512>(d, c, a, bf16, st, phase_in);
 }
 #else
-void launch_sess_frame_1536(const DspDev& d, const CellDev& c, const SessArgs& a, bool bf16, hipStream_t st);     // (dn_sessions1536.hip)
-void launch_sess_frame_512(const DspDev& d, const CellDev& c, const SessArgs& a, bool bf16, hipStream_t st);      // (dn_sessions512.hip)
+void launch_sess_frame_1536(const DspDev& d, const CellDev& c, const SessArgs& a, bool bf16, hipStream_t st, bool phase_in);     // (dn_sessions1536.hip)
+void launch_sess_frame_512(const DspDev& d, const CellDev& c, const SessArgs& a, bool bf16, hipStream_t st, bool phase_in);      // (dn_sessions512.hip)
 
-void launch_sess_frame(const DspDev& d, const CellDev& c, const SessArgs& a, bool bf16, hipStream_t st) {
-    if (d.n_fft == 1536) launch_sess_frame_1536(d, c, a, bf16, st);
-    else if (d.n_fft == 512) launch_sess_frame_512(d, c, a, bf16, st);
-    else launch_sess_frame_n<1024>(d, c, a, bf16, st);
+void launch_sess_frame(const DspDev& d, const CellDev& c, const SessArgs& a, bool bf16, hipStream_t st, bool phase_in) {
+    if (d.n_fft == 1536) launch_sess_frame_1536(d, c, a, bf16, st, phase_in);
+    else if (d.n_fft == 512) launch_sess_frame_512(d, c, a, bf16, st, phase_in);
+    else launch_sess_frame_n<1024>(d, c, a, bf16, st, phase_in);
 }
 
 // (re)open: slot ids[i] gets a zero ring, overlap-add line and hx, zero counters and the stream id sids_in[i]

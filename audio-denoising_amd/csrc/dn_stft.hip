@@ -17,6 +17,13 @@ __global__ __launch_bounds__(kStftThreads) void stft_kernel(DspDev d, const floa
     stft_body<NFFT, WRITE_SPEC, WRITE_MEL>(smem, d, frames, spec, mel, peak_out, flags, blockIdx.x, threadIdx.x);
 }
 
+// The unit phasors of the analysis STFT alone (dn_stft_phasors): the same body, so the bits the fused kernels store in input-phase mode.
+template <int NFFT>
+__global__ __launch_bounds__(kStftThreads) void stft_phasor_kernel(DspDev d, const float* __restrict__ frames, float2* __restrict__ phas, uint32_t flags) {
+    __shared__ __attribute__((aligned(16))) char smem[stft_smem<NFFT>()];
+    stft_body<NFFT, false, false, kStftThreads, true>(smem, d, frames, nullptr, nullptr, nullptr, flags, blockIdx.x, threadIdx.x, phas);
+}
+
 // MelScale alone (app3.py:193 without the log): one wavefront per (b,t) row.
 __global__ __launch_bounds__(64) void mel_kernel(DspDev d, const float* __restrict__ mag, float* __restrict__ mel) {
     __shared__ float row[Geo<1536>::kBins + 7];
@@ -51,6 +58,14 @@ void launch_stft(const DspDev& d, const float* frames, float* spec, float* mel, 
     if (d.n_fft == 1536) launch_stft_n<1536>(d, frames, spec, mel, peak, B, flags, st);
     else if (d.n_fft == 512) launch_stft_n<512>(d, frames, spec, mel, peak, B, flags, st);
     else launch_stft_n<1024>(d, frames, spec, mel, peak, B, flags, st);
+}
+
+void launch_stft_phasors(const DspDev& d, const float* frames, float* phas, int B, uint32_t flags, hipStream_t st) {
+    const dim3 grid(B), block(kStftThreads);
+    float2* ph = reinterpret_cast<float2*>(phas);
+    if (d.n_fft == 1536) hipLaunchKernelGGL(stft_phasor_kernel<1536>, grid, block, 0, st, d, frames, ph, flags);
+    else if (d.n_fft == 512) hipLaunchKernelGGL(stft_phasor_kernel<512>, grid, block, 0, st, d, frames, ph, flags);
+    else hipLaunchKernelGGL(stft_phasor_kernel<1024>, grid, block, 0, st, d, frames, ph, flags);
 }
 
 void launch_mel(const DspDev& d, const float* mag, float* mel, int rows, hipStream_t st) {

@@ -19,12 +19,28 @@ static __device__ unsigned long long g_stft_probe[8];   // diagnostic build: pha
 #define DN_SSTAMP(id) do { } while (0)
 #endif
 
+// The unit phasor u = X / |X| of a bin (input-phase mode, DN_PHASE_FROM_INPUT: the phases a Griffin-Lim chain starts from).  ONE reciprocal square root
+// of |X|^2 = fmaf(re, re, im * im), spelled with fmaf and the builtin so that every instantiation rounds alike; |X|^2 below the smallest normal float
+// (a bin that is zero, or whose square underflows: |X| < ~1.1e-19) counts as zero and gives (1, 0) = torch.polar(m, angle(0)) (server.py:208,216).
+// |u| is 1 to within the v_rsq_f32's 1 ulp and two roundings.  (|X|^2 must be finite: it is, for a frame that was peak-normalised.)
+__device__ __forceinline__ v2f unit_phasor(v2f x) {
+    const float p = fmaf(x[0], x[0], x[1] * x[1]);
+    const float r = __builtin_amdgcn_rsqf(p);
+    return p < 1.17549435e-38f ? mk2(1.0f, 0.0f) : mk2(x[0] * r, x[1] * r);
+}
+
 // One workgroup (192 threads = 3 wavefronts = 3 STFT columns) processes frame `b`.  `smem`: stft_smem<NFFT>() bytes of LDS.
 // THREADS > 192: the extra wavefront helps load / normalise the frame and then waits at the end (the three columns are three waves).
-template <int NFFT, bool WRITE_SPEC, bool WRITE_MEL, int THREADS = kStftThreads>
+// WRITE_PHASE: the unit phasors of the frame's bins go to `phas` [..][3][K] complex (row b), the layout of init_angles.  Wave w / lane l stores the bins
+// it holds after the split -- k = l + 64 t and NC - k (t < NP), lane 0 also NC / 2 -- which are exactly the bins wave w / lane l of gl_body loads as
+// its initial phases (both take NP and NC from Geo<NFFT>: n_fft 512, 1024 and 1536 alike).  A kernel that runs the chain behind this body in the SAME
+// workgroup therefore reads back only what the same lane wrote (bin NC / 2 is read by every lane of wave w and used by lane 0, which wrote it): program
+// order is all it needs, and every such kernel has a workgroup barrier in between anyway.
+template <int NFFT, bool WRITE_SPEC, bool WRITE_MEL, int THREADS = kStftThreads, bool WRITE_PHASE = false>
 __device__ __forceinline__ void stft_body(char* smem, const DspDev& d, const float* __restrict__ frames,
                                           float2* __restrict__ spec, float* __restrict__ mel,
-                                          float* __restrict__ peak_out, uint32_t flags, size_t b, int tid) {
+                                          float* __restrict__ peak_out, uint32_t flags, size_t b, int tid,
+                                          float2* __restrict__ phas = nullptr) {
     using G = Geo<NFFT>;
     constexpr int kNR = G::kNR, kHop = G::kHop, kBins = G::kBins, kNV = G::kNV, kNP = G::kNP, kFftTile = G::kTile;
     float* xs = reinterpret_cast<float*>(smem);
@@ -126,6 +142,15 @@ __device__ __forceinline__ void stft_body(char* smem, const DspDev& d, const flo
             srow[G::kNC - (lane + 64 * t)] = hi[t];
         }
         if (lane == 0) srow[G::kNC / 2] = mid;
+    }
+    if (WRITE_PHASE) {
+        v2f* prow = reinterpret_cast<v2f*>(phas) + (b * 3 + w) * kBins;
+#pragma unroll
+        for (int t = 0; t < kNP; ++t) {
+            prow[lane + 64 * t] = unit_phasor(lo[t]);
+            prow[G::kNC - (lane + 64 * t)] = unit_phasor(hi[t]);
+        }
+        if (lane == 0) prow[G::kNC / 2] = unit_phasor(mid);
     }
     if (WRITE_MEL) {
         // ---- P5: magnitude -> banded mel filterbank -> log1p; P6: rows are already (B,3,M)

@@ -24,10 +24,17 @@ class Denoiser:
     """Batched, fused hop pipeline bound to one model and one DSP plan on one GPU."""
 
     def __init__(self, model: GRUUNet2, sample_rate: int, n_fft: int = 1024, hop_length: int = 512, n_mels: int = 80,
-                 n_iter: int = 32, momentum: float = 0.99, device=None, window: torch.Tensor | None = None):
+                 n_iter: int = 32, momentum: float = 0.99, device=None, window: torch.Tensor | None = None, phase: str = "random"):
+        """``phase``: where a frame's Griffin-Lim chain starts.  ``"random"`` (default): the reference's random draw (app3.py:149-153).  ``"input"``: the
+        phases of the noisy frame's own STFT (DN_PHASE_FROM_INPUT) -- with ``n_iter=0`` the reconstruction of the reference's socket server
+        (server.py:208,216) inside the hop, with ``n_iter=k`` Griffin-Lim warm-started from the input.  Every front end built on this denoiser
+        inherits it; ``init_angles`` cannot be combined with it, and ``seed`` / ``stream_id0`` no longer matter for the phases."""
         self.device = torch.device(device if device is not None else next(model.parameters()).device)
         if self.device.type != "cuda":
             raise RuntimeError("Denoiser needs a 'cuda' device; there is no CPU path in this package")
+        if phase not in ("random", "input"):
+            raise ValueError("phase must be 'random' or 'input'")
+        self.phase = phase
         if n_mels % 16 != 0:
             raise ValueError("n_mels must be a multiple of 16 (four stride-2 encoder levels)")
         self.lib = _lib.get_lib()
@@ -45,14 +52,15 @@ class Denoiser:
         self._calls = 0
 
     def _flags(self) -> int:
-        """DN_CONV_BF16 when the model asks for bf16 MFMA conv tiles (GRUUNet2.conv_precision, BASELINE config 3)."""
+        """DN_CONV_BF16 when the model asks for bf16 MFMA conv tiles (GRUUNet2.conv_precision, BASELINE config 3); DN_PHASE_FROM_INPUT for
+        ``phase="input"``."""
         if self.model.conv_precision not in ("fp32", "bf16"):
             raise ValueError("conv_precision must be 'fp32' or 'bf16'")
-        return _lib.DN_CONV_BF16 if self.model.conv_precision == "bf16" else 0
+        return (_lib.DN_CONV_BF16 if self.model.conv_precision == "bf16" else 0) | (_lib.DN_PHASE_FROM_INPUT if self.phase == "input" else 0)
 
     # -- helpers
     def _workspace(self, batch: int) -> torch.Tensor:
-        need = self.plan.workspace_bytes(batch)
+        need = self.plan.workspace_bytes(batch, self._flags())
         if self._ws is None or self._ws.numel() < need:
             self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
         return self._ws
@@ -71,6 +79,8 @@ class Denoiser:
         """(B, K, 3) complex64 as the reference draws it -> [B][3][K] interleaved storage."""
         if init_angles is None:
             return None, None
+        if self.phase == "input":
+            raise ValueError("this denoiser takes its initial phases from the input (phase='input'): init_angles cannot be passed")
         if tuple(init_angles.shape) != (batch, self.n_stft, 3) or init_angles.dtype != torch.complex64:
             raise ValueError(f"init_angles must be complex64 of shape {(batch, self.n_stft, 3)}")
         ia = torch.view_as_real(init_angles.to(self.device).transpose(-1, -2).contiguous())
@@ -84,6 +94,19 @@ class Denoiser:
         with torch.cuda.device(self.device):
             st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
             self.lib.check(self.lib.dn_griffinlim_draw_phases(self.plan.handle, seed, stream_id0, buf.data_ptr(), batch, st))
+        return torch.view_as_complex(buf).transpose(-1, -2)
+
+    def input_phases(self, frames: torch.Tensor) -> torch.Tensor:
+        """The initial Griffin-Lim phases a ``phase="input"`` hop takes from ``frames`` (B, n_fft) (dn_stft_phasors): complex64 (B, n_fft/2+1, 3), the
+        unit phasors X / |X| of the 3-column STFT of the peak-normalised, pre-windowed frame ((1, 0) where X is zero).  The counterpart of
+        ``draw_phases``: passing it as ``init_angles`` to a ``phase="random"`` denoiser reproduces the ``phase="input"`` call bit for bit."""
+        B = frames.shape[0]
+        self._check(frames, (B, self.n_fft), "frames")
+        buf = torch.empty(B, 3, self.n_stft, 2, dtype=torch.float32, device=self.device)
+        with torch.cuda.device(self.device):
+            st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+            self.lib.check(self.lib.dn_stft_phasors(self.plan.handle, frames.data_ptr(), buf.data_ptr(), B,
+                                                    _lib.DN_PEAK_NORMALIZE | _lib.DN_PRE_WINDOW, st))
         return torch.view_as_complex(buf).transpose(-1, -2)
 
     # -- the hop body
@@ -122,6 +145,8 @@ class Denoiser:
         """hops n0 .. n0 + n of a sequence of (B, K, 3) complex64 -> [B][n][3][K] interleaved storage."""
         if per_hop is None:
             return None
+        if self.phase == "input":
+            raise ValueError("this denoiser takes its initial phases from the input (phase='input'): init_angles cannot be passed")
         hops = [per_hop[n0 + i] for i in range(n)]
         for ia in hops:
             if tuple(ia.shape) != (batch, self.n_stft, 3) or ia.dtype != torch.complex64:
@@ -149,7 +174,7 @@ class Denoiser:
                 tin = hops_in if whole else hops_in[:, n0 * self.hop:(n0 + n) * self.hop].contiguous()
                 tout = out if whole else torch.empty_like(tin)
                 ia = self._pack_clip_angles(init_angles_per_hop, B, n0, n)
-                need = self.lib.dn_clip_workspace_bytes(self.plan.handle, B, n)
+                need = self.lib.dn_clip_workspace_bytes_ex(self.plan.handle, B, n, self._flags())
                 if self._clip_ws is None or self._clip_ws.numel() < need:
                     self._clip_ws = torch.empty(need, dtype=torch.uint8, device=self.device)
                 self.lib.check(self.lib.dn_clip_process(model_h, self.plan.handle, tin.data_ptr(), int(s16), ring.data_ptr(), ola.data_ptr(),

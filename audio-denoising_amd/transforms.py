@@ -81,8 +81,9 @@ class DspPlan:
         self.lib.check(self.lib.dn_dsp_get_tables(self.handle, fb.data_ptr(), pinv.data_ptr(), win.data_ptr()))
         return fb[:, :self.n_mels], pinv[:, :self.n_mels], win
 
-    def workspace_bytes(self, batch: int) -> int:
-        return int(self.lib.dn_workspace_bytes(self.handle, batch))
+    def workspace_bytes(self, batch: int, flags: int = 0) -> int:
+        """Scratch of a fused call with ``flags`` (dn_workspace_bytes_ex: input-phase mode adds the phasor rows)."""
+        return int(self.lib.dn_workspace_bytes_ex(self.handle, batch, flags))
 
 
 def _stream_ptr(device):

@@ -17,6 +17,7 @@
  *   dn_dsp_create                       app3.py:135-155  construction of the torchaudio
  *                                       Spectrogram/MelScale/InverseMelScale/GriffinLim + Hann window
  *   dn_stft                             app3.py:191      Spectrogram(power=None)(x)
+ *   dn_stft_phasors                     server.py:208    spec.angle() of the noisy input, as unit phasors (DN_PHASE_FROM_INPUT)
  *   dn_stft_mel_log1p                   app3.py:179-195  peak-normalise, Hann, STFT, |.|, MelScale, log1p, transpose
  *   dn_mel_scale                        app3.py:193      MelScale(mag)
  *   dn_invmel / dn_residual_invmel      app3.py:203-211  leaky_relu(in-out), expm1, clamp, InverseMelScale, clamp
@@ -55,7 +56,7 @@
 extern "C" {
 #endif
 
-#define DN_ABI_VERSION 7
+#define DN_ABI_VERSION 8
 
 typedef enum dn_status {
     DN_OK = 0,
@@ -217,14 +218,39 @@ int dn_istft_general(const dn_dsp* d, const float* spec, float* wave, int32_t B,
 /* flags of the fused entry points */
 #define DN_CONV_BF16 1u /* BASELINE config 3: encoder/decoder convs on bf16 MFMA tiles (as dn_cell_forward_bf16); 0 = exact fp32 */
 
+/* ---- Input-phase mode: the Griffin-Lim chain starts from the phases of the noisy input ----------------------
+ * DN_PHASE_FROM_INPUT, a flag of every fused entry point (dn_process_frame, dn_stream_step, dn_clip_process per call; dn_pipe_create,
+ * dn_pipe_stream_create and dn_sessions_create for the life of the pipe or pool).  Let X[c][k] be the 3-column analysis STFT the hop computes
+ * anyway: the STFT of the peak-normalised, pre-windowed frame, whose magnitudes feed the mel.  With the flag the chain's initial phases are the unit
+ * phasors u = X / |X| instead of the reference's random draw (app3.py:149-153,213), and everything else is as before:
+ * out = GriffinLim(lin, init = u, n_iter, momentum) * peak, then the overlap-add; frame counters advance as before; `seed` and `stream_id0` are
+ * ignored for the phases.  n_iter = 0 is istft(polar(lin, angle(X))) -- the reconstruction of the reference's socket server (server.py:208,216:
+ * phase = spec.angle(); I0(torch.polar(O, phase))) inside the real-time hop; n_iter = k is Griffin-Lim warm-started from the input.
+ * Arithmetic: u = (re * r, im * r) with ONE reciprocal square root r = rsq(fmaf(re, re, im * im)), the same instructions in every kernel, so every
+ * entry point gives the same bits; a bin whose |X|^2 is below the smallest normal float (1.17549435e-38: |X| < ~1.1e-19, zero included) gets
+ * u = (1, 0), which is torch.polar(m, angle(0)) = m.
+ * The flag excludes init_angles: the per-call entry points return DN_ERR_INVALID for flag + non-NULL init_angles before anything is launched; a
+ * pipe or pool created with the flag returns it for every later submit / push that passes init_angles.  Either way nothing is changed.
+ * Off by default; without the flag every entry point computes what it did before. */
+#define DN_PHASE_FROM_INPUT 8u
+
+/* The phasors themselves: frames [dev][B][n_fft] -> phasors [dev][B][3][K] complex, the layout of init_angles.  flags as for dn_stft
+ * (DN_PEAK_NORMALIZE | DN_PRE_WINDOW is what the fused hops apply).  The same device code the fused kernels run, so the same bits: a call without
+ * DN_PHASE_FROM_INPUT that is handed these phasors as init_angles reproduces the call with the flag bit for bit. */
+int dn_stft_phasors(const dn_dsp* d, const float* frames, float* phasors, int32_t B, uint32_t flags, void* stream);
+
 /* Scratch the fused entry points need, in bytes, for a batch of B streams. */
 size_t dn_workspace_bytes(const dn_dsp* d, int32_t B);
+/* The same for a call with `flags`: dn_workspace_bytes(d, B) when DN_PHASE_FROM_INPUT is not set; with it, plus the phasor rows --
+ * 3 K complex values a stream, rounded up to 256 bytes.  (0 for unknown flag bits.) */
+size_t dn_workspace_bytes_ex(const dn_dsp* d, int32_t B, uint32_t flags);
 
 /* The whole per-hop body for B streams (app3.py:178-217): frames [dev][B][n_fft] raw samples,
  * hx [dev][B][17][C] in/out, out [dev][B][n_fft] = GriffinLim(...) * peak.
  * mel_residual_out [dev][B][3][M] or NULL receives the model output (predicted_diff_mel).
  * workspace [dev] of dn_workspace_bytes(d, B) bytes.  ONE launch (one workgroup per stream runs P1-P12 back to back);
- * no hop of added latency.  flags: DN_CONV_BF16 or 0. */
+ * no hop of added latency.  flags: DN_CONV_BF16, DN_PHASE_FROM_INPUT (then workspace of dn_workspace_bytes_ex(d, B, flags) bytes and
+ * init_angles NULL) or 0. */
 int dn_process_frame(const dn_model* m, const dn_dsp* d, const float* frames, float* hx, float* out,
                      float* mel_residual_out, const float* init_angles, uint64_t seed, uint64_t stream_id0,
                      int32_t n_iter, float momentum, void* workspace, int32_t B, uint32_t flags, void* stream);
@@ -232,7 +258,7 @@ int dn_process_frame(const dn_model* m, const dn_dsp* d, const float* frames, fl
 /* Streaming step (app3.py:178-226): ring [dev][B][n_fft] holds the last n_fft input samples per stream;
  * hop_in [dev][B][hop] new samples are shifted in first.  ola [dev][B][n_fft] is the output
  * overlap-add buffer; hop_out [dev][B][hop] receives ola[:hop] before the shift (app3.py:219-224).
- * ONE launch; every argument is validated before it, so a failed call leaves ring, ola and hx untouched. */
+ * ONE launch; every argument is validated before it, so a failed call leaves ring, ola and hx untouched.  flags as dn_process_frame. */
 int dn_stream_step(const dn_model* m, const dn_dsp* d, const float* hop_in, float* ring, float* ola, float* hx,
                    float* hop_out, const float* init_angles, uint64_t seed, uint64_t stream_id0, int32_t n_iter,
                    float momentum, void* workspace, int32_t B, uint32_t flags, void* stream);
@@ -256,6 +282,9 @@ int dn_stream_step(const dn_model* m, const dn_dsp* d, const float* hop_in, floa
 #define DN_CLIP_GL_PER_COLUMN 2u   /* chains: one workgroup per frame, a wavefront per column (gl_body)            */
 #define DN_CLIP_GL_PER_STREAM 4u   /* chains: a wavefront per frame, four frames a workgroup (glw_body; n_fft 1024, else DN_ERR_UNSUPPORTED) */
 size_t dn_clip_workspace_bytes(const dn_dsp* d, int32_t B, int32_t N);
+/* With DN_PHASE_FROM_INPUT in `flags` (the only bit that changes the size; the others a call may carry are accepted): plus the phasor rows of the
+ * B x N frames, 3 K complex each, rounded up to 256 bytes -- what dn_clip_process wants when called with that flag.  Else dn_clip_workspace_bytes. */
+size_t dn_clip_workspace_bytes_ex(const dn_dsp* d, int32_t B, int32_t N, uint32_t flags);
 int dn_clip_process(const dn_model* m, const dn_dsp* d, const void* hops_in, int32_t in_s16, float* ring, float* ola,
                     float* hx, void* hops_out, int32_t out_s16, const float* init_angles, uint64_t seed,
                     uint64_t stream_id0, int32_t n_iter, float momentum, void* workspace, int32_t B, int32_t N,
@@ -289,7 +318,9 @@ int dn_clip_process(const dn_model* m, const dn_dsp* d, const void* hops_in, int
  *
  * A pipe holds a reference on its model and plan: dn_model_destroy / dn_dsp_destroy while a pipe still uses them only drop
  * the creator's reference.  dn_pipe_set_model rebinds a pipe to other weights between two launches (launches already
- * enqueued keep reading the old model: keep it alive until they have run).  flags: DN_CONV_BF16 or 0. */
+ * enqueued keep reading the old model: keep it alive until they have run).  flags: DN_CONV_BF16, DN_PHASE_FROM_INPUT or 0.
+ * An input-phase pipe (DN_PHASE_FROM_INPUT) allocates the slots' init area at create, as dn_pipe_reserve_parity does, so a captured push allocates
+ * nothing: every front half leaves its frame's phasors there, in every mode (head start, either schedule, depth, split, groups). */
 typedef struct dn_pipe dn_pipe;
 int dn_pipe_create(const dn_model* m, const dn_dsp* d, int32_t B, uint32_t flags, dn_pipe** out);
 void dn_pipe_destroy(dn_pipe* p);
@@ -442,7 +473,8 @@ int dn_pipe_stream_set_state(dn_pipe* p, const float* ring, const float* ola, co
  *   DN_SESS_TWO_LAUNCHES  the front halves (P1-P10) of all listed slots, then their Griffin-Lim chains a wavefront per
  *                         session (n_fft 1024; DN_ERR_UNSUPPORTED at 512 and 1536); the same samples, bit for bit;
  *   DN_SESS_AUTO          (default) two launches from 1,024 listed slots on at n_fft 1024 (the measured crossover: DESIGN.md 4.11).
- * flags of dn_sessions_create: DN_CONV_BF16 or 0.  The pool holds a reference on its model and plan (as a dn_pipe). */
+ * flags of dn_sessions_create: DN_CONV_BF16, DN_PHASE_FROM_INPUT (the pool then holds phasor rows for its capacity; both schedules; records are the
+ * same, so a record exported from a pool in either mode imports into a pool in the other) or 0.  The pool holds a reference on its model and plan (as a dn_pipe). */
 typedef struct dn_sessions dn_sessions;
 #define DN_SESS_AUTO 0
 #define DN_SESS_ONE_LAUNCH 1
