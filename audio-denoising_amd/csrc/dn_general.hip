@@ -41,7 +41,7 @@ __global__ __launch_bounds__(64) void stft_general_kernel(DspDev d, const float*
     }
     G::Fft::template run<false>(v, tw, tile, lane);
     v2f lo[kNP], hi[kNP], mid;
-    rfft_split_pairs<kNV>(v, wkh, lane, lo, hi, mid);
+    rfft_split_pairs<kNV>(v, wkh, lane, tile, lo, hi, mid);
     if (spec != nullptr) {
         v2f* srow = reinterpret_cast<v2f*>(spec) + blk * kBins;
 #pragma unroll
@@ -133,7 +133,7 @@ __global__ __launch_bounds__(128) void istft_general_kernel(DspDev d, const floa
         hi[s] = srow[kNC - (lane + 64 * s)];
     }
     const v2f mid = srow[kNC / 2];
-    irfft_merge_pairs<kNV>(lo, hi, mid, wkh, lane, v);
+    irfft_merge_pairs<kNV>(lo, hi, mid, wkh, lane, tile[w], v);
     G::Fft::template run<true>(v, tw, tile[w], lane);
     // column j keeps samples n >= hop (registers s >= NP), column j+1 samples n < hop (s < NP)
     if (w == 0) {

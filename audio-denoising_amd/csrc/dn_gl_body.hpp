@@ -105,7 +105,8 @@ __device__ __forceinline__ void gl_body(char* smem, const DspDev& d, const float
 
     const int lane = tid & 63;
     const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
-    v2f* mytile = tile[w];
+    v2f* mytile = tile[w];             // exchange tile of this wave's transforms; between them it carries the pair-order hand-offs
+    static_assert(handoff_entries<kNV>() <= kFftTile, "the hand-off fits the exchange tile");
 
     // prologue scratch aliases the overlap-add lines (used only before the first iteration)
     float* mm = &ybuf[0][0][0];           // [3][128]      mel magnitudes
@@ -279,7 +280,7 @@ __device__ __forceinline__ void gl_body(char* smem, const DspDev& d, const float
         }
         // ---- istft of X = angles * magnitude: Hermitian merge, inverse FFT, synthesis window, overlap-add lines
         DN_STAMP(0);
-        irfft_merge_pairs<kNV>(xlo, xhi, xmid, wkh, lane, v);
+        irfft_merge_pairs<kNV>(xlo, xhi, xmid, wkh, lane, mytile, v);
         DN_STAMP(1);
         G::Fft::template run<true>(v, tw, mytile, lane, pd_t);
         DN_STAMP(2);
@@ -347,7 +348,7 @@ __device__ __forceinline__ void gl_body(char* smem, const DspDev& d, const float
         DN_STAMP(5);
         G::Fft::template run<false>(v, tw, mytile, lane, pd_t);
         DN_STAMP(6);
-        rfft_split_pairs<kNV>(v, wkh, lane, rlo, rhi, rmid);
+        rfft_split_pairs<kNV>(v, wkh, lane, mytile, rlo, rhi, rmid);
         DN_STAMP(7);
         // ---- phase update with momentum
 #pragma unroll

@@ -1,7 +1,7 @@
 // dn_glw_body.hpp -- Griffin-Lim with ONE WAVEFRONT PER STREAM: the schedule for the saturated regime (several streams per CU).
 //
 // dn_gl_body.hpp gives a stream's three STFT columns to three wavefronts: the shortest possible chain for ONE stream (what the batch-256
-// launch needs: one stream per CU), but each of those waves is a latency chain -- four LDS tile exchanges, two ds_bpermute rounds and a
+// launch needs: one stream per CU), but each of those waves is a latency chain -- four LDS tile exchanges, two pair hand-offs and a
 // workgroup barrier per iteration that nothing overlaps -- and with several streams per CU the machine stays latency bound: at 1,024 and
 // 8,192 streams the counters see the VALU busy 38 % of the time and 1.4 waves per SIMD (profiles/r03_pmc_saturated.txt).
 // Here a wavefront owns a whole stream:
@@ -95,6 +95,11 @@ __device__ __forceinline__ void glw_body(char* smem, const DspDev& d, const floa
     v2f* tile0 = reinterpret_cast<v2f*>(mine);
     v2f* tile1 = tile0 + kTile;
     float* sl = reinterpret_cast<float*>(mine + 8 * 2 * kTile);      // rebuilt signal s[0..n_fft), as of the last overlap-add
+    // the pair-order hand-offs of the three columns (rfft_split_pairs / irfft_merge_pairs) go through the two tiles, which are contiguous and free at
+    // both points: the forward group's last read of a tile precedes the splits' writes in program order, the merges' reads precede put0 of the inverse
+    // group (this wave's LDS operations execute in order).  One region per column: the three hand-offs of a direction are independent.
+    constexpr int kHand = handoff_entries<kNV>();
+    static_assert(3 * kHand <= 2 * kTile, "the hand-off regions of the three columns fit the two exchange tiles");
 
     typename G::Fft::Tw tw;
     G::Fft::template load<true>(tw, reinterpret_cast<const v2f*>(d.twc), lane);
@@ -126,9 +131,9 @@ __device__ __forceinline__ void glw_body(char* smem, const DspDev& d, const floa
     using XP = v2f[kNP];
     auto synthesize = [&](XP& x0lo, XP& x0hi, v2f x0mid, XP& x2lo, XP& x2hi, v2f x2mid, XP& x1lo, XP& x1hi, v2f x1mid) {
         v2f v[3][kNV];
-        irfft_merge_pairs<kNV>(x0lo, x0hi, x0mid, wkh, lane, v[0]);
-        irfft_merge_pairs<kNV>(x2lo, x2hi, x2mid, wkh, lane, v[1]);
-        irfft_merge_pairs<kNV>(x1lo, x1hi, x1mid, wkh, lane, v[2]);
+        irfft_merge_pairs<kNV>(x0lo, x0hi, x0mid, wkh, lane, tile0 + 0 * kHand, v[0]);
+        irfft_merge_pairs<kNV>(x2lo, x2hi, x2mid, wkh, lane, tile0 + 1 * kHand, v[1]);
+        irfft_merge_pairs<kNV>(x1lo, x1hi, x1mid, wkh, lane, tile0 + 2 * kHand, v[2]);
         fft(std::true_type{}, v);
 #pragma unroll
         for (int t = 0; t < kHalf; ++t) {
@@ -290,10 +295,10 @@ __device__ __forceinline__ void glw_body(char* smem, const DspDev& d, const floa
                 v[t] = s2 * cw_t[2 * kNC + lane + 64 * t];
             }
         };
-        auto advance = [&](const v2f (&v)[kNV], auto col, XP& xlo, XP& xhi, v2f& xmid) {       // split, phase update
+        auto advance = [&](const v2f (&v)[kNV], v2f* hand, auto col, XP& xlo, XP& xhi, v2f& xmid) {       // split, phase update
             constexpr int c = decltype(col)::value;
             v2f rlo[kNP], rhi[kNP], rmid;
-            rfft_split_pairs<kNV>(v, wkh, lane, rlo, rhi, rmid);
+            rfft_split_pairs<kNV>(v, wkh, lane, hand, rlo, rhi, rmid);
 #pragma unroll
             for (int t = 0; t < kNP; ++t) {
                 update(rlo[t], pin_lo[c][t], pout_lo[c][t], xlo[t], mlo[c][t]);
@@ -309,9 +314,9 @@ __device__ __forceinline__ void glw_body(char* smem, const DspDev& d, const floa
 #pragma unroll
             for (int t = 0; t < kNV; ++t) v[2][t] = snew[t] * cw_t[1 * kNC + lane + 64 * t];
             fft(std::false_type{}, v);
-            advance(v[0], std::integral_constant<int, 0>{}, x0lo, x0hi, x0mid);
-            advance(v[1], std::integral_constant<int, 2>{}, x2lo, x2hi, x2mid);
-            advance(v[2], std::integral_constant<int, 1>{}, x1lo, x1hi, x1mid);
+            advance(v[0], tile0 + 0 * kHand, std::integral_constant<int, 0>{}, x0lo, x0hi, x0mid);
+            advance(v[1], tile0 + 1 * kHand, std::integral_constant<int, 2>{}, x2lo, x2hi, x2mid);
+            advance(v[2], tile0 + 2 * kHand, std::integral_constant<int, 1>{}, x1lo, x1hi, x1mid);
         }
         synthesize(x0lo, x0hi, x0mid, x2lo, x2hi, x2mid, x1lo, x1hi, x1mid);
     };

@@ -131,7 +131,7 @@ __device__ __forceinline__ void stft_body(char* smem, const DspDev& d, const flo
     G::Fft::template run<false>(v, tw, tile[w], lane);
     // Hermitian split in pair order: this lane gets bins k = lane + 64 t and NC - k (t < NP); lane 0 also bin NC/2
     v2f lo[kNP], hi[kNP], mid;
-    rfft_split_pairs<kNV>(v, wkh, lane, lo, hi, mid);
+    rfft_split_pairs<kNV>(v, wkh, lane, tile[w], lo, hi, mid);
     DN_SSTAMP(4);
 
     if (WRITE_SPEC) {

@@ -177,30 +177,37 @@ template <> struct WaveFft<512> {
         }
     }
     // Padded tile index maps keep the scattered ds_write_b64 and the strided ds_read_b64 (nearly) conflict free.
-    static __device__ __forceinline__ int pad0(int c) { return c + (c >> 4); }
-    static __device__ __forceinline__ int pad1(int c) { return c + ((c >> 6) << 3); }
+    static constexpr int pad0(int c) { return c + (c >> 4); }
+    static constexpr int pad1(int c) { return c + ((c >> 6) << 3); }
+    // The same maps with the lane part hoisted: every index a pass uses is ONE lane-dependent value plus a compile-time constant, so the accesses of a
+    // pass share one address register and pair up (ds_read2_b64 / ds_write2_b64).  Written through pad0 / pad1 the sum reaches the backend as
+    // lane + ((lane >> 4) | 4 t): an `or` that no addressing mode folds, i.e. one address register and one single access per value.
+    //     pad0(8 lane + t)       = w0(lane) + t          pad0(lane + 64 t) = r0(lane) + 68 t
+    //     pad1(base(lane) + 8 t) = w1(lane) + 8 t        pad1(lane + 64 t) = lane + 72 t               (t = 0..7; checked below the struct)
+    static constexpr int w0(int lane) { return 8 * lane + (lane >> 1); }
+    static constexpr int r0(int lane) { return lane + (lane >> 4); }
+    static constexpr int base1(int lane) { return ((lane >> 3) << 6) + (lane & 7); }
+    static constexpr int w1(int lane) { return base1(lane) + ((lane >> 3) << 3); }
 
     template <bool INV>
     static __device__ __forceinline__ void run(v2f (&v)[8], const Tw& tw, v2f* tile, int lane, const v2f* = nullptr) {
+        const int iw0 = w0(lane), ir0 = r0(lane), iw1 = w1(lane);
         dft8<INV>(v);                                         // pass 0 (Ns = 1)
         wave_sync();                                          // previous readers of the tile are done
 #pragma unroll
-        for (int t = 0; t < 8; ++t) tile[pad0(8 * lane + t)] = v[t];
+        for (int t = 0; t < 8; ++t) tile[iw0 + t] = v[t];
         wave_sync();
 #pragma unroll
-        for (int t = 0; t < 8; ++t) v[t] = tile[pad0(lane + 64 * t)];
+        for (int t = 0; t < 8; ++t) v[t] = tile[ir0 + 68 * t];
 #pragma unroll
         for (int t = 1; t < 8; ++t) v[t] = twmul<INV>(v[t], tw.p1[t - 1]);    // pass 1 (Ns = 8)
         dft8<INV>(v);
         wave_sync();
-        {
-            const int base = ((lane >> 3) << 6) + (lane & 7);
 #pragma unroll
-            for (int t = 0; t < 8; ++t) tile[pad1(base + 8 * t)] = v[t];
-        }
+        for (int t = 0; t < 8; ++t) tile[iw1 + 8 * t] = v[t];
         wave_sync();
 #pragma unroll
-        for (int t = 0; t < 8; ++t) v[t] = tile[pad1(lane + 64 * t)];
+        for (int t = 0; t < 8; ++t) v[t] = tile[lane + 72 * t];
 #pragma unroll
         for (int t = 1; t < 8; ++t) v[t] = twmul<INV>(v[t], tw.p2[t - 1]);    // pass 2 (Ns = 64): output stays in registers
         dft8<INV>(v);
@@ -212,26 +219,26 @@ template <> struct WaveFft<512> {
     // wave_sync()s are compiler barriers only.  Same arithmetic as run().
     template <bool INV, int NB>
     static __device__ __forceinline__ void run_n(v2f (&v)[NB][8], const Tw& tw, v2f* const (&tile)[NB], int lane) {
-        const int base = ((lane >> 3) << 6) + (lane & 7);
+        const int iw0 = w0(lane), ir0 = r0(lane), iw1 = w1(lane);
         auto put0 = [&](int c) {
             wave_sync();
 #pragma unroll
-            for (int t = 0; t < 8; ++t) tile[c][pad0(8 * lane + t)] = v[c][t];
+            for (int t = 0; t < 8; ++t) tile[c][iw0 + t] = v[c][t];
             wave_sync();
         };
         auto get0 = [&](int c) {
 #pragma unroll
-            for (int t = 0; t < 8; ++t) v[c][t] = tile[c][pad0(lane + 64 * t)];
+            for (int t = 0; t < 8; ++t) v[c][t] = tile[c][ir0 + 68 * t];
         };
         auto put1 = [&](int c) {
             wave_sync();
 #pragma unroll
-            for (int t = 0; t < 8; ++t) tile[c][pad1(base + 8 * t)] = v[c][t];
+            for (int t = 0; t < 8; ++t) tile[c][iw1 + 8 * t] = v[c][t];
             wave_sync();
         };
         auto get1 = [&](int c) {
 #pragma unroll
-            for (int t = 0; t < 8; ++t) v[c][t] = tile[c][pad1(lane + 64 * t)];
+            for (int t = 0; t < 8; ++t) v[c][t] = tile[c][lane + 72 * t];
         };
         auto pass1 = [&](int c) {
 #pragma unroll
@@ -260,6 +267,17 @@ template <> struct WaveFft<512> {
     }
 };
 
+constexpr bool wavefft512_folded_maps_hold() {
+    using F = WaveFft<512>;
+    for (int lane = 0; lane < 64; ++lane)
+        for (int t = 0; t < 8; ++t)
+            if (F::w0(lane) + t != F::pad0(8 * lane + t) || F::r0(lane) + 68 * t != F::pad0(lane + 64 * t) ||
+                F::w1(lane) + 8 * t != F::pad1(F::base1(lane) + 8 * t) || lane + 72 * t != F::pad1(lane + 64 * t))
+                return false;
+    return true;
+}
+static_assert(wavefft512_folded_maps_hold(), "the hoisted tile indices of WaveFft<512> are pad0 / pad1");
+
 template <> struct WaveFft<768> {
     static constexpr int kNV = 12;
     static constexpr int kTile = 960;        // 768 + padding of the widest map
@@ -284,8 +302,17 @@ template <> struct WaveFft<768> {
 #pragma unroll
         for (int r = 1; r < 12; ++r) pd_lds[(r - 1) * 64 + lane] = twc[lane * r];
     }
-    static __device__ __forceinline__ int padA(int c) { return c + (c >> 4); }
-    static __device__ __forceinline__ int padB(int c) { return c + ((c >> 4) << 2); }
+    static constexpr int padA(int c) { return c + (c >> 4); }
+    static constexpr int padB(int c) { return c + ((c >> 4) << 2); }
+    // the lane parts of the maps, hoisted as in WaveFft<512> (j = lane + 64 g, g = 0..2; r = 0..3; t = 0..11; checked below the struct):
+    //     padA(4 j + r)                      = wA(lane) + 272 g + r          padA(lane + 64 t) = rA(lane) + 68 t
+    //     padB(16 (j>>2) + (j&3) + 4 r)      = wB(lane) + 320 g + 4 r        padB(lane + 64 t) = rB(lane) + 80 t
+    //          64 (j>>4) + (j&15) + 16 r     = wC(lane) + 256 g + 16 r
+    static constexpr int wA(int lane) { return 4 * lane + (lane >> 2); }
+    static constexpr int rA(int lane) { return lane + (lane >> 4); }
+    static constexpr int wB(int lane) { return 20 * (lane >> 2) + (lane & 3); }
+    static constexpr int rB(int lane) { return lane + ((lane >> 4) << 2); }
+    static constexpr int wC(int lane) { return 64 * (lane >> 4) + (lane & 15); }
 
     // one radix-4 pass over the three butterflies of a lane (registers v[g], v[g+3], v[g+6], v[g+9])
     template <bool INV, bool TWIDDLE>
@@ -303,33 +330,34 @@ template <> struct WaveFft<768> {
 
     template <bool INV>
     static __device__ __forceinline__ void run(v2f (&v)[12], const Tw& tw, v2f* tile, int lane, const v2f* pd_lds = nullptr) {
+        const int iwA = wA(lane), irA = rA(lane), iwB = wB(lane), irB = rB(lane), iwC = wC(lane);
         // pass A (R=4, Ns=1): out[4 j + r], j = lane + 64 g
         pass4<INV, false>(v, tw.pb);
         wave_sync();
 #pragma unroll
         for (int g = 0; g < 3; ++g)
 #pragma unroll
-            for (int r = 0; r < 4; ++r) tile[padA(4 * (lane + 64 * g) + r)] = v[g + 3 * r];
+            for (int r = 0; r < 4; ++r) tile[iwA + 272 * g + r] = v[g + 3 * r];
         wave_sync();
 #pragma unroll
-        for (int t = 0; t < 12; ++t) v[t] = tile[padA(lane + 64 * t)];
+        for (int t = 0; t < 12; ++t) v[t] = tile[irA + 68 * t];
         // pass B (R=4, Ns=4): out[16 (j>>2) + (j&3) + 4 r]
         pass4<INV, true>(v, tw.pb);
         wave_sync();
 #pragma unroll
         for (int g = 0; g < 3; ++g)
 #pragma unroll
-            for (int r = 0; r < 4; ++r) tile[padB(16 * ((lane + 64 * g) >> 2) + (lane & 3) + 4 * r)] = v[g + 3 * r];
+            for (int r = 0; r < 4; ++r) tile[iwB + 320 * g + 4 * r] = v[g + 3 * r];
         wave_sync();
 #pragma unroll
-        for (int t = 0; t < 12; ++t) v[t] = tile[padB(lane + 64 * t)];
+        for (int t = 0; t < 12; ++t) v[t] = tile[irB + 80 * t];
         // pass C (R=4, Ns=16): out[64 (j>>4) + (j&15) + 16 r]  (conflict free without padding)
         pass4<INV, true>(v, tw.pc);
         wave_sync();
 #pragma unroll
         for (int g = 0; g < 3; ++g)
 #pragma unroll
-            for (int r = 0; r < 4; ++r) tile[64 * ((lane + 64 * g) >> 4) + (lane & 15) + 16 * r] = v[g + 3 * r];
+            for (int r = 0; r < 4; ++r) tile[iwC + 256 * g + 16 * r] = v[g + 3 * r];
         wave_sync();
 #pragma unroll
         for (int t = 0; t < 12; ++t) v[t] = tile[lane + 64 * t];
@@ -344,6 +372,23 @@ template <> struct WaveFft<768> {
         dft12<INV>(v);
     }
 };
+
+constexpr bool wavefft768_folded_maps_hold() {
+    using F = WaveFft<768>;
+    for (int lane = 0; lane < 64; ++lane) {
+        for (int g = 0; g < 3; ++g)
+            for (int r = 0; r < 4; ++r) {
+                const int j = lane + 64 * g;
+                if (F::wA(lane) + 272 * g + r != F::padA(4 * j + r) || F::wB(lane) + 320 * g + 4 * r != F::padB(16 * (j >> 2) + (j & 3) + 4 * r) ||
+                    F::wC(lane) + 256 * g + 16 * r != 64 * (j >> 4) + (j & 15) + 16 * r)
+                    return false;
+            }
+        for (int t = 0; t < 12; ++t)
+            if (F::rA(lane) + 68 * t != F::padA(lane + 64 * t) || F::rB(lane) + 80 * t != F::padB(lane + 64 * t)) return false;
+    }
+    return true;
+}
+static_assert(wavefft768_folded_maps_hold(), "the hoisted tile indices of WaveFft<768> are padA / padB");
 
 // ---- geometry of the real transform ----------------------------------------------------------------
 template <int NFFT> struct Geo {
@@ -369,26 +414,52 @@ template <int NFFT> struct Geo {
 // Bins k and NC-k are produced together, so the lane that owns k = lane + 64 t (t < NP) also owns
 // NC-k ("pair order"): the split, any per-bin work and the merge are then lane-local and only the
 // FFT-order <-> pair-order hand-off crosses lanes.  That hand-off is the fixed involution
-// (lane j, reg t) <-> (lane 64-j, reg NV-1-t), done with ds_bpermute (no LDS memory, no barrier).
-// Lane 0 pairs with itself: (0,NC), (64,NC-64), .. and the self-paired bin NC/2.
+// (lane j, reg t) <-> (lane 64-j, reg NV-1-t).  Lane 0 pairs with itself: (0,NC), (64,NC-64), .. and the self-paired bin NC/2,
+// and its pairs sit one register further (Z[NC - 64 t] = own v[NV - t]).
 // `wkh[t]` = 1/2 W^k for k = lane + 64 t, t = 0..NP-1.
+//
+// The hand-off goes through `h`: (NP + 1) * 64 complex entries of wave-private LDS that are free at the call (the wave's exchange tile: the
+// transform in front has read it out, the one behind has not written yet; LDS operations of one wave execute in order).  Every lane writes NP + 1
+// rows at column `lane` -- the NP values its partner wants and, in the last row, the one value lane 0 wants from itself -- and reads NP values back
+// from ONE address with constant row offsets:
+//     src = ((64 - lane) & 63) + (lane == 0 ? 64 : 0)        lanes 1..63: the partner's column;  lane 0: its own column, one row further
+// so lane 0's special case is an address, not a select per value.  NP + 1 writes and NP reads of 8 bytes (ds_write2st64_b64 / ds_read2st64_b64: the
+// rows are 64 entries apart) replace NV ds_bpermute_b32 and as many v_cndmask per direction, at the cost of one LDS round trip -- what a permute round
+// costs as well.  Banks (8-byte entries, as above: a write conflicts within 16 consecutive lanes, a read within a half of the wave,
+// bank pair = entry % 32):
+//   writes  the lanes of a group hit 16 consecutive entries of a row.  Conflict free.
+//   reads   row offsets are multiples of 64 and drop out mod 32.  Lanes 0..31 read columns {0 or 64, 63, 62, .. 33}: mod 32 that is 0 and
+//           31 .. 1; lanes 32..63 read columns {32, 31, .. 1}: mod 32 that is 0 and 31 .. 1.  All different.  Conflict free.
+// -DDN_HANDOFF_BPERMUTE keeps the earlier form -- ds_bpermute (no LDS memory), lane 0 handled with per-value selects on the sending / receiving side
+// (not with a divergent block: a block forces `s_waitcnt lgkmcnt(0)` at its head) -- for A/B runs and for a translation unit that measures slower.
 __device__ __forceinline__ v2f shfl2(v2f v, int src) { return mk2(__shfl(v[0], src), __shfl(v[1], src)); }
-
-// Lane 0 is its own partner and its pairs sit one register further (Z[NC - 64 t] = own v[NV - t]); both directions handle that with
-// per-value selects on the sending / receiving side (v_cndmask), not with a divergent block: a block forces `s_waitcnt lgkmcnt(0)` at its
-// head, i.e. every permute has to be back before the first pair can be combined.
 __device__ __forceinline__ v2f sel2(bool c, v2f a, v2f b) { return mk2(c ? a[0] : b[0], c ? a[1] : b[1]); }
+template <int NV> constexpr int handoff_entries() { return (NV / 2 + 1) * 64; }
+__device__ __forceinline__ int handoff_src(int lane) { return ((64 - lane) & 63) + (lane == 0 ? 64 : 0); }
 
 // Forward: v[t] = Z[lane + 64 t] -> lo[t] = X[k], hi[t] = X[NC-k]; mid = X[NC/2] (meaningful in lane 0).
 template <int NV>
-__device__ __forceinline__ void rfft_split_pairs(const v2f (&v)[NV], const v2f (&wkh)[NV / 2], int lane,
+__device__ __forceinline__ void rfft_split_pairs(const v2f (&v)[NV], const v2f (&wkh)[NV / 2], int lane, v2f* h,
                                                  v2f (&lo)[NV / 2], v2f (&hi)[NV / 2], v2f& mid) {
     constexpr int NP = NV / 2;
+    v2f zp[NP];
+#ifdef DN_HANDOFF_BPERMUTE
     const int partner = (64 - lane) & 63;
     const bool l0 = lane == 0;
-    v2f zp[NP];
 #pragma unroll
     for (int t = 0; t < NP; ++t) zp[t] = shfl2(sel2(l0, t == 0 ? v[0] : v[NV - t], v[NV - 1 - t]), partner);
+#else
+    // rows r < NP: v[NP + r]; row NP: v[0].  Lanes 1..63 read the partner's v[NV - 1 - t] from row NP - 1 - t; lane 0 reads its own row NP - t:
+    // v[0] for t = 0, v[NV - t] behind it.
+    const int src = handoff_src(lane);
+    wave_sync();                                               // previous readers of the tile are done
+#pragma unroll
+    for (int r = 0; r < NP; ++r) h[64 * r + lane] = v[NP + r];
+    h[64 * NP + lane] = v[0];
+    wave_sync();
+#pragma unroll
+    for (int t = 0; t < NP; ++t) zp[t] = h[64 * (NP - 1 - t) + src];
+#endif
 #pragma unroll
     for (int t = 0; t < NP; ++t) {
         const v2f s = cadd_conj(v[t], zp[t]);                  // Z + conj Zp
@@ -402,7 +473,7 @@ __device__ __forceinline__ void rfft_split_pairs(const v2f (&v)[NV], const v2f (
 // Inverse: lo[t] = X[k], hi[t] = X[NC-k], mid = X[NC/2] -> v[t] = Z[lane + 64 t] ready for IFFT_NC.
 template <int NV>
 __device__ __forceinline__ void irfft_merge_pairs(v2f (&lo)[NV / 2], v2f (&hi)[NV / 2], v2f mid,
-                                                  const v2f (&wkh)[NV / 2], int lane, v2f (&v)[NV]) {
+                                                  const v2f (&wkh)[NV / 2], int lane, v2f* h, v2f (&v)[NV]) {
     constexpr int NP = NV / 2;
     const bool l0 = lane == 0;
     lo[0][1] = l0 ? 0.0f : lo[0][1];                           // Im X[0], Im X[NC] are ignored (C2R convention)
@@ -415,14 +486,27 @@ __device__ __forceinline__ void irfft_merge_pairs(v2f (&lo)[NV / 2], v2f (&hi)[N
         v[t] = chalf_add_pi(s, dd);                                  // s/2 + i dd
         zh[t] = chalf_conj_add_iconj(s, dd);                         // conj(s/2) + i conj(dd)
     }
+    const v2f cm = mk2(mid[0], -mid[1]);
+#ifdef DN_HANDOFF_BPERMUTE
     const int partner = (64 - lane) & 63;
     v2f r[NP];
 #pragma unroll
     for (int t = 0; t < NP; ++t) r[t] = shfl2(zh[t], partner);
     // lanes 1..63: v[NV-1-t] = r[t];  lane 0 (received its own zh): v[NV-t] = r[t] for t >= 1 and v[NP] = conj(mid)
-    const v2f cm = mk2(mid[0], -mid[1]);
 #pragma unroll
     for (int t = 0; t < NP; ++t) v[NV - 1 - t] = sel2(l0, t + 1 < NP ? r[t + 1] : cm, r[t]);
+#else
+    // rows t < NP: zh[t]; row NP: conj(mid).  Lanes 1..63 read the partner's zh[t] into v[NV - 1 - t]; lane 0 reads its own row t + 1:
+    // zh[t + 1], and conj(mid) for v[NP].
+    const int src = handoff_src(lane);
+    wave_sync();                                               // previous readers of the tile are done
+#pragma unroll
+    for (int t = 0; t < NP; ++t) h[64 * t + lane] = zh[t];
+    h[64 * NP + lane] = cm;
+    wave_sync();
+#pragma unroll
+    for (int t = 0; t < NP; ++t) v[NV - 1 - t] = h[64 * t + src];
+#endif
 }
 
 }  // namespace dn

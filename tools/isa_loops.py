@@ -1,7 +1,9 @@
 #!/usr/bin/env python3
 """Instruction histogram of the big loops of one kernel in a hipcc -S listing (tools: which instructions a Griffin-Lim
-iteration really issues).  usage: isa_loops.py listing.s kernel-substring [min_body]"""
+iteration really issues).  usage: isa_loops.py listing.s kernel-substring [min_body [all]]
+LDS accesses are split into paired (ds_rd2, ds_wr2: two values from one address register) and single ones (ds_rd1, ds_wr1)."""
 import re
+import subprocess
 import sys
 from collections import Counter
 
@@ -14,6 +16,11 @@ def classify(op):
     if op.startswith("v_cndmask"): return "v_cndmask"
     if op.startswith("v_"): return "v_other"
     if op.startswith("ds_bpermute"): return "ds_bperm"
+    # LDS reads and writes, paired (ds_read2_b64, ds_read2st64_b64, ..: two values, one address register) and single
+    if op.startswith("ds_read2") or op.startswith("ds_load_2addr"): return "ds_rd2"
+    if op.startswith("ds_read") or op.startswith("ds_load"): return "ds_rd1"
+    if op.startswith("ds_write2") or op.startswith("ds_store_2addr"): return "ds_wr2"
+    if op.startswith("ds_write") or op.startswith("ds_store"): return "ds_wr1"
     if op.startswith("ds_"): return "ds"
     if op.startswith("global_") or op.startswith("buffer_") or op.startswith("flat_"): return "vmem"
     if op.startswith("scratch_"): return "scratch"
@@ -28,8 +35,20 @@ def classify(op):
 def main():
     path, kern = sys.argv[1], sys.argv[2]
     min_body = int(sys.argv[3]) if len(sys.argv) > 3 else 150
+    every = len(sys.argv) > 4 and sys.argv[4] == "all"          # every kernel whose name holds the substring, not the first one only
     lines = open(path).read().split("\n")
-    start = next(i for i, l in enumerate(lines) if l.startswith("_Z") and kern in l and l.rstrip().split(":")[0].endswith(l.split(":")[0]))
+    starts = [i for i, l in enumerate(lines) if re.match(r"^_Z\w+:", l) and kern in l]
+    if not starts:
+        sys.exit(f"no kernel with {kern!r} in its name in {path}")
+    for start in starts if every else starts[:1]:
+        if every:
+            name = lines[start].split(":")[0]
+            dem = subprocess.run(["c++filt", name], capture_output=True, text=True).stdout.strip()
+            print("\n" + re.sub(r"^void |\(.*$", "", dem))
+        one_kernel(lines, start, min_body)
+
+
+def one_kernel(lines, start, min_body):
     end = next(i for i in range(start + 1, len(lines)) if lines[i].startswith(".Lfunc_end"))
     body = lines[start:end]
     # blocks
