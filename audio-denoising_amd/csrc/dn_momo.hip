@@ -139,10 +139,9 @@ __global__ __launch_bounds__(kMomoThreads) void momo_kernel(MomoDev md, const fl
 }  // namespace dn
 
 // ------------------------------------------------------------------ host side: packing + C ABI
-namespace {
+#include "dn_host.hpp"
 
-thread_local std::string g_momo_err;
-int mfail(int code, const std::string& msg);
+namespace {
 
 struct MomoLayout {     // state_dict order of momo3.MOMO3 (offsets in floats)
     size_t dw[3], db[3], off_in, gw, gb, off_rs, uw[3], ub[3], total;
@@ -160,7 +159,7 @@ struct MomoLayout {     // state_dict order of momo3.MOMO3 (offsets in floats)
 };
 
 struct MomoTables {
-    float* dev = nullptr;
+    DevBuf<float> dev;
     dn::MomoDev view;
 };
 
@@ -169,20 +168,13 @@ struct MomoTables {
 struct dn_momo {
     dn_momo_cfg cfg;
     std::vector<float> w;
-    float* packed = nullptr;               // weight fragments of the seven conv levels
+    DevBuf<float> packed;                  // weight fragments of the seven conv levels
     size_t off_af[7];
-    std::mutex mu;
-    std::map<int, MomoTables*> tables;     // per input length F (bias tables depend on the lengths)
+    mutable std::mutex mu;
+    mutable std::map<int, std::unique_ptr<MomoTables>> tables;     // per input length F (bias tables depend on the lengths)
 };
 
-const char* dn_last_error_set(const char* msg);     // dn_api.hip: sets the calling thread's error string
-
 namespace {
-
-int mfail(int code, const std::string& msg) {
-    dn_last_error_set(msg.c_str());
-    return code;
-}
 
 // torch.linspace(0, 1, n) in fp32 (the CPU kernel's symmetric formula) and the GaussianSmearing table (momo3.py:54-68)
 std::vector<float> lin01(int n) {
@@ -222,10 +214,10 @@ std::vector<float> pack_level(const float* W, bool transposed, int cin_data, int
 
 int conv_len(int L, int pad, int stride) { return (L + 2 * pad - 3) / stride + 1; }
 
-int build_tables(dn_momo* m, int F, MomoTables** out) {
+int build_tables(const dn_momo* m, int F, const MomoTables** out) {
     std::lock_guard<std::mutex> lock(m->mu);
     auto it = m->tables.find(F);
-    if (it != m->tables.end()) { *out = it->second; return DN_OK; }
+    if (it != m->tables.end()) { *out = it->second.get(); return DN_OK; }
     const MomoLayout ml;
     const float* W = m->w.data();
     const int* pd = m->cfg.paddings;
@@ -273,15 +265,14 @@ int build_tables(dn_momo* m, int F, MomoTables** out) {
     off_bt[4] = plain(ml.ub[0], 16, L2);
     off_bt[5] = plain(ml.ub[1], 16, L1);
     off_bt[6] = plain(ml.ub[2], 1, F);
-    MomoTables* t = new MomoTables();
-    hipError_t e = hipMalloc(reinterpret_cast<void**>(&t->dev), host.size() * sizeof(float));
-    if (e == hipSuccess) e = hipMemcpy(t->dev, host.data(), host.size() * sizeof(float), hipMemcpyHostToDevice);
-    if (e != hipSuccess) { if (t->dev) (void)hipFree(t->dev); delete t; return mfail(DN_ERR_HIP, std::string("MOMO3 bias tables: ") + hipGetErrorString(e)); }
+    auto t = std::make_unique<MomoTables>();
+    const hipError_t e = t->dev.alloc_copy(host.data(), host.size() * sizeof(float));
+    if (e != hipSuccess) return fail(DN_ERR_HIP, std::string("MOMO3 bias tables: ") + hipGetErrorString(e));
     dn::MomoDev& v = t->view;
     v.F = F; v.L1 = L1; v.L2 = L2; v.C = C;
     auto lvl = [&](int idx, int cin, int cout, int lin, int lout, int stride, int pad) {
         dn::MomoLevel l;
-        l.af = m->packed + m->off_af[idx]; l.bt = t->dev + off_bt[idx];
+        l.af = m->packed.get() + m->off_af[idx]; l.bt = t->dev.get() + off_bt[idx];
         l.cin = cin; l.cout = cout; l.lin = lin; l.lout = lout; l.stride = stride; l.pad = pad;
         return l;
     };
@@ -292,8 +283,7 @@ int build_tables(dn_momo* m, int F, MomoTables** out) {
     v.dec[0] = lvl(4, 16, 16, C, L2, 2, pd[2]);       // UpBlocks walks the levels backwards (momo3.py:176-178)
     v.dec[1] = lvl(5, 32, 16, L2, L1, 2, pd[1]);
     v.dec[2] = lvl(6, 32, 1, L1, F, 2, pd[0]);
-    m->tables[F] = t;
-    *out = t;
+    *out = (m->tables[F] = std::move(t)).get();
     return DN_OK;
 }
 
@@ -302,14 +292,14 @@ int build_tables(dn_momo* m, int F, MomoTables** out) {
 extern "C" {
 
 int dn_momo_create(const float* weights, size_t n_floats, const dn_momo_cfg* cfg, dn_momo** out) {
-    if (!weights || !cfg || !out) return mfail(DN_ERR_INVALID, "dn_momo_create: null argument");
+    if (!weights || !cfg || !out) return fail(DN_ERR_INVALID, "dn_momo_create: null argument");
     const MomoLayout ml;
     if (cfg->in_size != 1 || cfg->n_levels != 3 || cfg->hidden_size != 16 || cfg->kernel_size != 3 || cfg->stride != 2 || cfg->num_gaussians != 6)
-        return mfail(DN_ERR_UNSUPPORTED, "MOMO3 kernels are built for in_size 1, 3 levels, hidden 16, k3 s2, 6 gaussians (saves/MOMO3-4d4ea0)");
+        return fail(DN_ERR_UNSUPPORTED, "MOMO3 kernels are built for in_size 1, 3 levels, hidden 16, k3 s2, 6 gaussians (saves/MOMO3-4d4ea0)");
     for (int l = 0; l < 3; ++l)
-        if (cfg->paddings[l] < 0 || cfg->paddings[l] > 1) return mfail(DN_ERR_UNSUPPORTED, "MOMO3 paddings must be 0 or 1");
-    if (n_floats != ml.total) return mfail(DN_ERR_INVALID, "expected " + std::to_string(ml.total) + " weight floats, got " + std::to_string(n_floats));
-    dn_momo* m = new dn_momo();
+        if (cfg->paddings[l] < 0 || cfg->paddings[l] > 1) return fail(DN_ERR_UNSUPPORTED, "MOMO3 paddings must be 0 or 1");
+    if (n_floats != ml.total) return fail(DN_ERR_INVALID, "expected " + std::to_string(ml.total) + " weight floats, got " + std::to_string(n_floats));
+    std::unique_ptr<dn_momo> m(new dn_momo());
     m->cfg = *cfg;
     m->w.assign(weights, weights + n_floats);
     const float* W = m->w.data();
@@ -322,45 +312,36 @@ int dn_momo_create(const float* weights, size_t n_floats, const dn_momo_cfg* cfg
     add(4, pack_level(W + ml.uw[0], true, 16, 16, 16));
     add(5, pack_level(W + ml.uw[1], true, 32, 32, 16));
     add(6, pack_level(W + ml.uw[2], true, 32, 32, 1));
-    hipError_t e = hipMalloc(reinterpret_cast<void**>(&m->packed), host.size() * sizeof(float));
-    if (e == hipSuccess) e = hipMemcpy(m->packed, host.data(), host.size() * sizeof(float), hipMemcpyHostToDevice);
-    if (e != hipSuccess) { if (m->packed) (void)hipFree(m->packed); delete m; return mfail(DN_ERR_HIP, std::string("MOMO3 weight upload: ") + hipGetErrorString(e)); }
-    *out = m;
+    const hipError_t e = m->packed.alloc_copy(host.data(), host.size() * sizeof(float));
+    if (e != hipSuccess) return fail(DN_ERR_HIP, std::string("MOMO3 weight upload: ") + hipGetErrorString(e));
+    *out = m.release();
     return DN_OK;
 }
 
-void dn_momo_destroy(dn_momo* m) {
-    if (!m) return;
-    for (auto& kv : m->tables) { (void)hipFree(kv.second->dev); delete kv.second; }
-    if (m->packed) (void)hipFree(m->packed);
-    delete m;
-}
+void dn_momo_destroy(dn_momo* m) { delete m; }
 
 int dn_momo_forward(const dn_momo* m, const float* x, const float* hx_in, const float* prev_in, float* out, float* hx_out,
                     float* prev_out, int32_t B, int32_t T, int32_t F, int32_t C, void* stream) {
     if (B == 0) return DN_OK;
-    if (!m || !x || !out || !hx_out) return mfail(DN_ERR_INVALID, "dn_momo_forward: null argument");
-    if (B < 0 || T < 0) return mfail(DN_ERR_INVALID, "dn_momo_forward: negative size");
-    if (F < 3 || F > dn::kMomoMaxF) return mfail(DN_ERR_UNSUPPORTED, "MOMO3 kernel supports 3..64 input bins");
+    if (!m || !x || !out || !hx_out) return fail(DN_ERR_INVALID, "dn_momo_forward: null argument");
+    if (B < 0 || T < 0) return fail(DN_ERR_INVALID, "dn_momo_forward: negative size");
+    if (F < 3 || F > dn::kMomoMaxF) return fail(DN_ERR_UNSUPPORTED, "MOMO3 kernel supports 3..64 input bins");
     const int* pd = m->cfg.paddings;
     const int L1 = conv_len(F, pd[0], 2), L2 = L1 >= 1 ? conv_len(L1, pd[1], 2) : 0, Cx = L2 >= 1 ? conv_len(L2, pd[2], 2) : 0;
-    if (L1 < 1 || L2 < 1 || Cx < 1) return mfail(DN_ERR_INVALID, "input is too short for three stride-2 levels");
+    if (L1 < 1 || L2 < 1 || Cx < 1) return fail(DN_ERR_INVALID, "input is too short for three stride-2 levels");
     if (Cx != C)
-        return mfail(DN_ERR_INVALID, "input of " + std::to_string(F) + " bins compresses to " + std::to_string(Cx) + ", but hx has " +
+        return fail(DN_ERR_INVALID, "input of " + std::to_string(F) + " bins compresses to " + std::to_string(Cx) + ", but hx has " +
                                          std::to_string(C) + " compressed bins");
-    if (C > dn::kMomoMaxC) return mfail(DN_ERR_UNSUPPORTED, "too many compressed bins");
+    if (C > dn::kMomoMaxC) return fail(DN_ERR_UNSUPPORTED, "too many compressed bins");
     // the decoder must be able to reach the skip lengths with output_padding 0 or 1 (ConvTranspose1d output_size, momo3.py:185-187)
     const int up0 = (C - 1) * 2 - 2 * pd[2] + 3, up1 = (L2 - 1) * 2 - 2 * pd[1] + 3, up2 = (L1 - 1) * 2 - 2 * pd[0] + 3;
     if (L2 - up0 < 0 || L2 - up0 > 1 || L1 - up1 < 0 || L1 - up1 > 1 || F - up2 < 0 || F - up2 > 1)
-        return mfail(DN_ERR_INVALID, "requested output size is not reachable by the transposed convs (as the reference raises)");
-    MomoTables* t = nullptr;
-    int rc = build_tables(const_cast<dn_momo*>(m), F, &t);
-    if (rc != DN_OK) return rc;
+        return fail(DN_ERR_INVALID, "requested output size is not reachable by the transposed convs (as the reference raises)");
+    const MomoTables* t = nullptr;
+    DN_TRY(build_tables(m, F, &t));
     hipLaunchKernelGGL(dn::momo_kernel, dim3(B), dim3(dn::kMomoThreads), 0, reinterpret_cast<hipStream_t>(stream), t->view, x, hx_in, prev_in, out,
                        hx_out, prev_out, T);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return mfail(DN_ERR_HIP, std::string("momo_kernel launch: ") + hipGetErrorString(e));
-    return DN_OK;
+    return check_launch("momo_kernel");
 }
 
 }  // extern "C"

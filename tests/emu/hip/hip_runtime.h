@@ -45,7 +45,22 @@ typedef int hipError_t;
 constexpr hipError_t hipSuccess = 0;
 typedef struct dn_emu_stream* hipStream_t;
 enum hipMemcpyKind { hipMemcpyHostToDevice, hipMemcpyDeviceToHost, hipMemcpyDeviceToDevice };
-inline hipError_t hipMalloc(void** p, size_t n) { *p = malloc(n); return *p ? 0 : 1; }
+// Fault injection for the test of the host layer (tests/emu/host_faults.cpp): DN_EMU_FAIL_AT=n makes the n-th resource-creating call of the
+// process (hipMalloc, hipHostMalloc, stream creation, event creation) fail, once.  Unset (or 0): never.  The countdown is the program's to reset.
+namespace dn_emu {
+inline long& fail_countdown() {
+    static long n = [] { const char* e = getenv("DN_EMU_FAIL_AT"); return e ? atol(e) : 0L; }();
+    return n;
+}
+inline bool inject_failure() {
+    long& n = fail_countdown();
+    return n > 0 && --n == 0;
+}
+}  // namespace dn_emu
+inline hipError_t hipMalloc(void** p, size_t n) {
+    *p = dn_emu::inject_failure() ? nullptr : malloc(n);
+    return *p ? 0 : 1;
+}
 inline hipError_t hipFree(void* p) { free(p); return 0; }
 inline hipError_t hipMemcpy(void* d, const void* s, size_t n, hipMemcpyKind) { memcpy(d, s, n); return 0; }
 inline hipError_t hipGetLastError() { return 0; }
@@ -53,18 +68,25 @@ inline hipError_t hipMemcpyAsync(void* d, const void* s, size_t n, hipMemcpyKind
 inline hipError_t hipMemset(void* p, int v, size_t n) { memset(p, v, n); return 0; }
 inline hipError_t hipMemsetAsync(void* p, int v, size_t n, hipStream_t) { memset(p, v, n); return 0; }
 struct short4 { short x, y, z, w; };
-// streams and events: the emulation is synchronous, so these only have to exist
+// streams and events: the emulation is synchronous, so these only have to exist -- as one-byte allocations, so that one that leaks or is
+// destroyed twice shows under a sanitizer
 typedef struct dn_emu_event* hipEvent_t;
 constexpr unsigned hipStreamNonBlocking = 1, hipEventDisableTiming = 2;
-inline hipError_t hipStreamCreateWithFlags(hipStream_t* s, unsigned) { *s = nullptr; return 0; }
-inline hipError_t hipStreamDestroy(hipStream_t) { return 0; }
+inline hipError_t hipStreamCreateWithFlags(hipStream_t* s, unsigned) {
+    *s = dn_emu::inject_failure() ? nullptr : static_cast<hipStream_t>(malloc(1));
+    return *s ? 0 : 1;
+}
+inline hipError_t hipStreamDestroy(hipStream_t s) { free(s); return 0; }
 inline hipError_t hipStreamSynchronize(hipStream_t) { return 0; }
 constexpr hipError_t hipErrorNotReady = 600;
 inline hipError_t hipStreamQuery(hipStream_t) { return 0; }          // (launches run to completion inside the launch call)
 inline hipError_t hipDeviceSynchronize() { return 0; }
 inline hipError_t hipStreamWaitEvent(hipStream_t, hipEvent_t, unsigned) { return 0; }
-inline hipError_t hipEventCreateWithFlags(hipEvent_t* e, unsigned) { *e = nullptr; return 0; }
-inline hipError_t hipEventDestroy(hipEvent_t) { return 0; }
+inline hipError_t hipEventCreateWithFlags(hipEvent_t* e, unsigned) {
+    *e = dn_emu::inject_failure() ? nullptr : static_cast<hipEvent_t>(malloc(1));
+    return *e ? 0 : 1;
+}
+inline hipError_t hipEventDestroy(hipEvent_t e) { free(e); return 0; }
 inline hipError_t hipEventRecord(hipEvent_t, hipStream_t) { return 0; }
 inline hipError_t hipEventSynchronize(hipEvent_t) { return 0; }
 // pointer attributes: everything is "host pageable" here, so the staged path of dn_pipe_stream_push_host is what the emulation runs
@@ -77,7 +99,10 @@ inline hipError_t hipPointerGetAttributes(hipPointerAttribute_t* a, const void*)
     return 0;
 }
 inline hipError_t hipHostGetDevicePointer(void** d, void* h, unsigned) { *d = h; return 0; }
-inline hipError_t hipHostMalloc(void** p, size_t n, unsigned) { *p = malloc(n); return *p ? 0 : 1; }
+inline hipError_t hipHostMalloc(void** p, size_t n, unsigned) {
+    *p = dn_emu::inject_failure() ? nullptr : malloc(n);
+    return *p ? 0 : 1;
+}
 inline hipError_t hipHostFree(void* p) { free(p); return 0; }
 // system-scope fence / store: the emulation is one process, sequentially consistent atomics will do
 inline void __threadfence_system() { __atomic_thread_fence(__ATOMIC_SEQ_CST); }

@@ -10,7 +10,7 @@ Bars are the project's for the same stage, imported from tests/test_gpu_parity.p
 sample 0).  Small shapes: the emulator runs a work-item per OS thread; the gpu tier (tests/test_gpu_windows.py) runs the batches.
 
 What these tests catch and the Hann tests do not was tried on a scratch copy with two edits, one at a time (54 emulation tests from before,
-the 33 here).  (a) dn_api.hip builds the wave-per-stream tables of columns 0 and 2 from column 1's source indices: 8 of the 54 fail -- the
+the 33 here).  (a) dn_api_dsp.hip builds the wave-per-stream tables of columns 0 and 2 from column 1's source indices: 8 of the 54 fail -- the
 schedule bit-identities, which see column 2's two-sample envelope shift under Hann too (tests/dsp_cases.py names them) -- and 8 of the 33,
 every pipe, group and session case here.  (b) dn_gl_body.hpp drops column 0's reflection: all 54 pass, 14 of the 33 fail -- the eleven
 asymmetric-window cases that run Griffin-Lim, against float64, and three Hamming cases (pipe / depth 2, groups of 2 and 4) through the bit
