@@ -107,18 +107,25 @@ std::vector<float> bias_up(const float* W, const StateLayout& sl, int l, int C) 
 }
 
 // MFMA A fragments (v_mfma_f32_16x16x4_f32): lane l of k-step ks supplies W[o = 16 mt + (l & 15)][K slot 4 ks + (l >> 4)].
-// Conv1d weight (Cout, Ct, 3) of encoder level l: K order tap-major, channels in fours -> [mt][ks][64]
+// Conv1d weight (Cout, Ct, 3) of encoder level l: K order tap-major, channels in fours -> [mt][ks][64].  In front of the last, partial row tile
+// (channel 16; rows 48..50 of the 51-row level) lies the table of the same rows for the VALU lanes that compute them (dn_cell_body.hpp: rows_down):
+// [row][ks] float4 = the weights of the four K slots of k-step ks, zero-padded to whole 256-byte lines.
 std::vector<float> pack_down(const float* W, const StateLayout& sl, int l) {
     const int cd = l == 0 ? 1 : 17, ct = cd + 6, co = l == 3 ? 51 : 17;
     const int cs = (cd + 3) / 4, ks_n = cd == 1 ? 1 : 3 * cs, mtiles = (co + 15) / 16;
-    std::vector<float> p((size_t)mtiles * ks_n * 64, 0.0f);
+    const int rows = co % 16, row0 = co - rows, rt = dn::cell_rowtab_floats(rows, ks_n);
+    const auto weight = [&](int o, int ks, int q) {
+        const int tap = cd == 1 ? q : ks / cs, c = cd == 1 ? 0 : 4 * (ks % cs) + q;
+        return o < co && tap < 3 && c < cd ? W[sl.dw[l] + ((size_t)o * ct + c) * 3 + tap] : 0.0f;
+    };
+    std::vector<float> p((size_t)mtiles * ks_n * 64 + rt, 0.0f);
     for (int mt = 0; mt < mtiles; ++mt)
         for (int ks = 0; ks < ks_n; ++ks)
-            for (int ln = 0; ln < 64; ++ln) {
-                const int o = mt * 16 + (ln & 15), q = ln >> 4;
-                const int tap = cd == 1 ? q : ks / cs, c = cd == 1 ? 0 : 4 * (ks % cs) + q;
-                if (o < co && tap < 3 && c < cd) p[((size_t)mt * ks_n + ks) * 64 + ln] = W[sl.dw[l] + ((size_t)o * ct + c) * 3 + tap];
-            }
+            for (int ln = 0; ln < 64; ++ln)
+                p[((size_t)mt * ks_n + ks) * 64 + ln + (mt == mtiles - 1 ? rt : 0)] = weight(mt * 16 + (ln & 15), ks, ln >> 4);
+    for (int r = 0; r < rows; ++r)
+        for (int ks = 0; ks < ks_n; ++ks)
+            for (int q = 0; q < 4; ++q) p[(size_t)(mtiles - 1) * ks_n * 64 + ((size_t)r * ks_n + ks) * 4 + q] = weight(row0 + r, ks, q);
     return p;
 }
 
@@ -145,16 +152,21 @@ std::vector<float> pack_up(const float* W, const StateLayout& sl, int l) {
                 for (int set = 0; set < 3; ++set) p[((size_t)part * 17 + c) * 4 + set] = W[sl.uw[3] + ((size_t)(part * 17 + c)) * 3 + kTapOfSet[set]];
         return p;
     }
-    const int parts = l == 0 ? 1 : 2, co = 17, ksu = parts * 5, mtiles = (co + 15) / 16;
-    std::vector<float> p((size_t)mtiles * 3 * ksu * 64, 0.0f);
+    // in front of the second row tile (channel 16): that channel's table for rows_up, [ks][tap set] float4 = the four K slots of k-step ks
+    const int parts = l == 0 ? 1 : 2, co = 17, ksu = parts * 5, mtiles = (co + 15) / 16, rt = dn::cell_rowtab_floats(1, 3 * ksu);
+    const auto weight = [&](int o, int set, int ks, int q) {
+        const int cp = 4 * (ks % 5) + q, c = (ks / 5) * 17 + cp;
+        return o < co && cp < 17 ? W[sl.uw[l] + ((size_t)c * co + o) * 3 + kTapOfSet[set]] : 0.0f;
+    };
+    std::vector<float> p((size_t)mtiles * 3 * ksu * 64 + rt, 0.0f);
     for (int mt = 0; mt < mtiles; ++mt)
         for (int set = 0; set < 3; ++set)
             for (int ks = 0; ks < ksu; ++ks)
-                for (int ln = 0; ln < 64; ++ln) {
-                    const int o = mt * 16 + (ln & 15), q = ln >> 4, cp = 4 * (ks % 5) + q, c = (ks / 5) * 17 + cp;
-                    if (o < co && cp < 17)
-                        p[(((size_t)mt * 3 + set) * ksu + ks) * 64 + ln] = W[sl.uw[l] + ((size_t)c * co + o) * 3 + kTapOfSet[set]];
-                }
+                for (int ln = 0; ln < 64; ++ln)
+                    p[(((size_t)mt * 3 + set) * ksu + ks) * 64 + ln + (mt == mtiles - 1 ? rt : 0)] = weight(mt * 16 + (ln & 15), set, ks, ln >> 4);
+    for (int ks = 0; ks < ksu; ++ks)
+        for (int set = 0; set < 3; ++set)
+            for (int q = 0; q < 4; ++q) p[(size_t)(mtiles - 1) * 3 * ksu * 64 + ((size_t)ks * 3 + set) * 4 + q] = weight(16, set, ks, q);
     return p;
 }
 
@@ -229,12 +241,12 @@ int build_bias(const dn_model* m, int C, const BiasSet** out) {
 
 namespace {
 
-enum CellKind { kCellFp32, kCellEx, kCellBf16 };
+enum CellKind { kCellFp32, kCellEx, kCellBf16, kCellParentTiles };
 
 int cell_forward(CellKind kind, const dn_model* m, const float* x, const float* hx_in, float* out, float* hx_out, int32_t B, int32_t T,
                  int32_t F, int32_t C, float hx_out_scale, void* stream) {
-    static const char* const kWho[] = {"dn_cell_forward", "dn_cell_forward_ex", "dn_cell_forward_bf16"};
-    static const char* const kKernel[] = {"cell_kernel", "cell_kernel_ex", "cell_kernel_bf16"};
+    static const char* const kWho[] = {"dn_cell_forward", "dn_cell_forward_ex", "dn_cell_forward_bf16", "dn_cell_forward_parent_tiles"};
+    static const char* const kKernel[] = {"cell_kernel", "cell_kernel_ex", "cell_kernel_bf16", "cell_kernel (parent tiles)"};
     if (B == 0) return DN_OK;      // empty batch: nothing to do (pointers of empty tensors are null)
     if (!m || !x || !out || !hx_out) return fail(DN_ERR_INVALID, std::string(kWho[kind]) + ": null argument");
     if (B < 0 || T < 0) return fail(DN_ERR_INVALID, std::string(kWho[kind]) + ": negative size");
@@ -246,6 +258,7 @@ int cell_forward(CellKind kind, const dn_model* m, const float* x, const float* 
     const BiasSet* bs = nullptr;
     DN_TRY(build_bias(m, C, &bs));
     if (kind == kCellFp32) dn::launch_cell(bs->view, x, hx_in, out, hx_out, B, T, C, as_stream(stream));
+    else if (kind == kCellParentTiles) dn::launch_cell_parent_tiles(bs->view, x, hx_in, out, hx_out, B, T, C, as_stream(stream));
     else if (kind == kCellEx) dn::launch_cell_ex(bs->view, x, hx_in, out, hx_out, B, T, C, hx_out_scale, as_stream(stream));
     else dn::launch_cell_bf16(bs->view, x, hx_in, out, hx_out, B, T, C, as_stream(stream));
     return check_launch(kKernel[kind]);
@@ -294,6 +307,12 @@ int dn_cell_forward_ex(const dn_model* m, const float* x, const float* hx_in, fl
 
 int dn_cell_forward_bf16(const dn_model* m, const float* x, const float* hx_in, float* out, float* hx_out, int32_t B, int32_t T, int32_t F, int32_t C, void* stream) {
     return cell_forward(kCellBf16, m, x, hx_in, out, hx_out, B, T, F, C, 0.0f, stream);
+}
+
+// dn_cell_forward on the conv tiles as they were before the live-row / lane-geometry change (dn_cell_body.hpp: TILES = 0).  For comparisons (tests,
+// tools/): declared in dn_internal.hpp, not part of include/dn_denoise.h, and nothing in the product calls it.
+int dn_cell_forward_parent_tiles(const dn_model* m, const float* x, const float* hx_in, float* out, float* hx_out, int32_t B, int32_t T, int32_t F, int32_t C, void* stream) {
+    return cell_forward(kCellParentTiles, m, x, hx_in, out, hx_out, B, T, F, C, 0.0f, stream);
 }
 
 }  // extern "C"

@@ -19,7 +19,10 @@
 //     ([m-tile][k-step][64 lanes], one coalesced 256-B load each); the B fragments are the
 //     im2col view of the LDS activations -- one ds_read_b32 per lane per k-step at a computed
 //     address, no staging copy.  1,024 MACs per instruction instead of 64: the per-stream
-//     forward is latency-bound on instruction issue, so this is what shortens it;
+//     forward is latency-bound on instruction issue, so this is what shortens it.  The tiles cover
+//     whole row tiles only: channel 16 of a 17-channel level (rows 48..50 of the 51-row encoder
+//     level) is the same fmaf chain on VALU lanes, one lane per (row, item) -- a second row tile
+//     spent as many MFMAs again on one live row in sixteen;
 //   * bottleneck hidden gates (51 channels x C positions, N too small for a tile): lane =
 //     (gate channel, position) on the VALU with that lane's 51 recurrent weights pinned in VGPRs
 //     across time steps; the single-channel last decoder level: lane = (t, position), VALU.
@@ -30,12 +33,13 @@ namespace dn {
 constexpr int kCellWaves = 4;
 
 // CT / TC: the compressed bin count and the number of time steps when they are the usual ones (5 or 4 bins, the hop's 3 columns), 0 = run time
-template <int CT, int TC>
+// TILES: the variant of the fp32 conv tiles (dn_cell_body.hpp); 0 = the tiles before the live-row / lane-geometry change (launch_cell_parent_tiles)
+template <int CT, int TC, int TILES = DN_CELL_TILES>
 __global__ __launch_bounds__(kCellWaves * 64) void cell_kernel(CellDev cd, const float* __restrict__ x,
                                                               const float* __restrict__ hx_in, float* __restrict__ out,
                                                               float* __restrict__ hx_out, int T, int C) {
     __shared__ __attribute__((aligned(16))) char smem[kCellSmem];
-    cell_body<kCellWaves, false, CT>(smem, cd, x, hx_in, out, hx_out, TC ? TC : T, C, blockIdx.x, threadIdx.x);
+    cell_body<kCellWaves, false, CT, kCellStageDefault, TILES>(smem, cd, x, hx_in, out, hx_out, TC ? TC : T, C, blockIdx.x, threadIdx.x);
 }
 
 // BASELINE config 3: the same forward with bf16 MFMA conv tiles (v_mfma_f32_16x16x32_bf16; conv inputs and weights
@@ -52,6 +56,15 @@ void launch_cell(const CellDev& c, const float* x, const float* hx_in, float* ou
     auto k = cell_kernel<0, 0>;
     if (C == 5) k = T == kCellChunk ? cell_kernel<5, kCellChunk> : cell_kernel<5, 0>;
     else if (C == 4) k = T == kCellChunk ? cell_kernel<4, kCellChunk> : cell_kernel<4, 0>;
+    hipLaunchKernelGGL(k, dim3(B), dim3(kCellWaves * 64), 0, st, c, x, hx_in, out, hx_out, T, C);
+}
+
+// The same forward on the tiles as they were (comparison only: tests and tools/; nothing in the product calls it).
+void launch_cell_parent_tiles(const CellDev& c, const float* x, const float* hx_in, float* out, float* hx_out, int B, int T,
+                              int C, hipStream_t st) {
+    auto k = cell_kernel<0, 0, 0>;
+    if (C == 5) k = T == kCellChunk ? cell_kernel<5, kCellChunk, 0> : cell_kernel<5, 0, 0>;
+    else if (C == 4) k = T == kCellChunk ? cell_kernel<4, kCellChunk, 0> : cell_kernel<4, 0, 0>;
     hipLaunchKernelGGL(k, dim3(B), dim3(kCellWaves * 64), 0, st, c, x, hx_in, out, hx_out, T, C);
 }
 

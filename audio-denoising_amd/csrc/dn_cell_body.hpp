@@ -31,6 +31,44 @@ static __device__ unsigned long long g_cell_probe[32];
 #define DN_CSTAMP_IN(id) do { } while (0)
 #endif
 
+// ---- Variants of the fp32 conv tiles (template switch TILES of the tile functions and of cell_body; bits):
+//   kTilesLiveRows  the rows of a partial last row tile (channel 16 of the 17-channel levels, rows 48..50 of the 51-row levels) are fmaf chains
+//                   on VALU lanes (rows_down / rows_up), one lane per (row, item), in the K order of the MFMA path; the MFMA tiles cover whole
+//                   row tiles only;
+//   kTilesLaneGeom  an item's time step comes from two compares (a chunk has at most three steps) and every multiple of it from selects: no
+//                   division and no integer multiply by a lane value in a tile.
+// 0 = the tiles as they were before either (kept for comparison: dn_cell_forward_parent_tiles).  DN_CELL_TILES is the build knob behind the default.
+constexpr int kTilesLiveRows = 1, kTilesLaneGeom = 2;
+#ifndef DN_CELL_TILES
+#define DN_CELL_TILES 3
+#endif
+// The one-launch hops (frame_kernel, sess_frame_kernel: nothing overlapped, the forward on the critical path) keep the tiles as they were: measured,
+// the serial hop loses 4.8 % with kTilesLaneGeom, 5.2 % with kTilesLiveRows and 5.9 % with both; the results are the same bits.
+#ifndef DN_FRAME_TILES
+#define DN_FRAME_TILES 0
+#endif
+static_assert(kCellChunk <= 3, "ItemPos tells the time step of an item by two compares");
+
+// Item of a level (clamped to a real one) -> its time step t inside the chunk and its position p = item - t * len.
+template <bool GEOM>
+struct ItemPos {
+    int t, p;
+    bool t1, t2;
+    __device__ __forceinline__ ItemPos(int itc, int len) {
+        if (GEOM) {
+            t1 = itc >= len;
+            t2 = itc >= 2 * len;
+            t = 0;
+            p = itc - (t2 ? 2 * len : t1 ? len : 0);
+        } else {
+            t1 = t2 = false;
+            t = itc / len;
+            p = itc - t * len;
+        }
+    }
+    __device__ __forceinline__ int times(int stride) const { return GEOM ? (t2 ? 2 * stride : t1 ? stride : 0) : t * stride; }   // t * stride
+};
+
 // Rows 16 mt + 4 q + r (r = 0..3) of one accumulator tile -> relu -> dst[row * stride]; see the note on exec-mask regions below.
 template <int COUT>
 __device__ __forceinline__ void store_rows(const f32x4& acc, float* dst, int stride, int mt, int q, float* trash) {
@@ -78,41 +116,53 @@ __device__ __forceinline__ void store_rows2(const f32x4& ev, const f32x4& od, fl
 //     address instead of a predicated store;
 //   * operands next to an edge are loaded unconditionally (one word outside the buffer at most, still inside the LDS plan) and
 //     zeroed by a select.
-template <int NW, int CIN, int COUT, int MT>
+//
+// TILES (see above).  With kTilesLiveRows the tiles cover the COUT / 16 whole row tiles and rows_down computes the other rows; the fragments of the
+// partial row tile lie behind the row table (RT floats) either way.
+template <int NW, int CIN, int COUT, int MT, int TILES = 0>
 __device__ __forceinline__ void mconv_down(const float* afrag, const float* bt, const float* in,
                                            float* out, float* trash, int lout, int tt, int wv, int lane) {
+    constexpr bool LIVE = (TILES & kTilesLiveRows) != 0, GEOM = (TILES & kTilesLaneGeom) != 0;
     constexpr int CS = (CIN + 3) / 4;
     constexpr int KS = CIN == 1 ? 1 : 3 * CS;
-    constexpr int MTILES = (COUT + 15) / 16;
+    constexpr int MTILES = LIVE ? COUT / 16 : (COUT + 15) / 16;
     constexpr int MG = MTILES / MT;
+    constexpr int RT = COUT % 16 ? cell_rowtab_floats(COUT % 16, KS) : 0;
+    constexpr int CROWS = LIVE ? MTILES * 16 : COUT;                     // rows the tiles store
+    static_assert(MTILES % MT == 0, "row tiles in whole groups");
     const int lin = 2 * lout, items = tt * lout, ntiles = (items + 15) >> 4;
     const int q = lane >> 4, jl = lane & 15;
     for (int tile = wv; tile < ntiles * MG; tile += NW) {
-        const int nt = tile % ntiles, mt0 = (tile / ntiles) * MT;
+        const int nt = GEOM && MG == 1 ? tile : tile % ntiles, mt0 = GEOM && MG == 1 ? 0 : (tile / ntiles) * MT;
         const int item = nt * 16 + jl;
         const bool valid = item < items;
         const int itc = valid ? item : 0;
-        const int t = itc / lout, p = itc - t * lout;
+        const ItemPos<GEOM> ip(itc, lout);
+        const int p = ip.p;
+        float* const dst = out + ip.times(COUT * lout) + p;              // (taken here: the selects behind times() end with the prologue)
         f32x4 acc[MT];
 #pragma unroll
         for (int mi = 0; mi < MT; ++mi)
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 const int o = (mt0 + mi) * 16 + q * 4 + r;
-                acc[mi][r] = bt[min(o, COUT - 1) * lout + p];
+                acc[mi][r] = bt[(LIVE ? o : min(o, COUT - 1)) * lout + p];
             }
         const float* af = afrag + (size_t)mt0 * KS * 64 + lane;
+        int tail[MT];                                                    // the partial row tile's fragments lie behind the row table
+#pragma unroll
+        for (int mi = 0; mi < MT; ++mi) tail[mi] = RT != 0 && mt0 + mi == COUT / 16 ? RT : 0;
         if (CIN == 1) {
-            const int idx = t * lin + 2 * p - 1 + q;
+            const int idx = ip.times(lin) + 2 * p - 1 + q;
             const bool ok = q < 3 && !(q == 0 && p == 0);
             float b = in[idx];
             b = ok ? b : 0.0f;
 #pragma unroll
-            for (int mi = 0; mi < MT; ++mi) acc[mi] = mfma16(af[mi * KS * 64], b, acc[mi]);
+            for (int mi = 0; mi < MT; ++mi) acc[mi] = mfma16(af[mi * KS * 64 + tail[mi]], b, acc[mi]);
         } else {
             // every operand of the tile is requested before the first MFMA: fetched a k-step at a time, each step paid an LDS round
             // trip (~150 cycles) in front of its 32-cycle MFMA
-            const float* base = in + (size_t)t * CIN * lin + 2 * p - 1;
+            const float* base = in + ip.times(CIN * lin) + 2 * p - 1;
             float bv[KS], av[MT][KS];
 #pragma unroll
             for (int tap = 0; tap < 3; ++tap)
@@ -126,7 +176,7 @@ __device__ __forceinline__ void mconv_down(const float* afrag, const float* bt, 
 #pragma unroll
             for (int mi = 0; mi < MT; ++mi)
 #pragma unroll
-                for (int ks = 0; ks < KS; ++ks) av[mi][ks] = af[(mi * KS + ks) * 64];
+                for (int ks = 0; ks < KS; ++ks) av[mi][ks] = af[(mi * KS + ks) * 64 + tail[mi]];
             __builtin_amdgcn_sched_barrier(0);
             if (CIN == kHidden && COUT == kHidden && MT == 2) DN_CSTAMP_IN(18);
 #pragma unroll
@@ -136,10 +186,69 @@ __device__ __forceinline__ void mconv_down(const float* afrag, const float* bt, 
             if (CIN == kHidden && COUT == kHidden && MT == 2) DN_CSTAMP_IN(19);
         }
 #pragma unroll
-        for (int mi = 0; mi < MT; ++mi) store_rows<COUT>(acc[mi], out + (size_t)t * COUT * lout + p, lout, mt0 + mi, q, trash);
+        for (int mi = 0; mi < MT; ++mi) store_rows<CROWS>(acc[mi], dst, lout, mt0 + mi, q, trash);
     }
 }
 
+// The rows of a level's partial last row tile (kTilesLiveRows): rows ROW0 = 16 (COUT / 16) .. COUT - 1.  One lane per (row, item), elements dealt
+// to the waves 64 at a time starting with wave `w0` (the one the tile loop of mconv_down would give its next tile).  A lane's result is the fmaf
+// chain the MFMA path runs for that accumulator element: it starts from the same bias entry and takes the K slots in the same order -- k-steps in
+// order, slots q = 0..3 inside a k-step, the zero-weight pad slots (which read the last channel, as the padded B lanes do) included -- so it is the
+// same float, non-finite inputs included.  rowtab: [ROWS][KS] float4 = the weights of the four slots of a k-step.  Lanes past the last element
+// work on element 0 again and store its value once more.
+template <int NW, int CIN, int COUT, bool GEOM>
+__device__ __forceinline__ void rows_down(const float* rowtab, const float* bt, const float* in, float* out, int lout, int tt, int wv,
+                                          int lane, int w0) {
+    static_assert((NW & (NW - 1)) == 0, "waves are dealt modulo a power of two");
+    constexpr int CS = (CIN + 3) / 4;
+    constexpr int KS = CIN == 1 ? 1 : 3 * CS;
+    constexpr int ROWS = COUT % 16, ROW0 = COUT - ROWS;
+    static_assert(ROWS >= 1 && ROWS <= 3, "the row of an element comes from two compares");
+    const int lin = 2 * lout, items = tt * lout, n = ROWS * items;
+    const float4* w4 = reinterpret_cast<const float4*>(rowtab);
+    for (int e0 = ((wv - w0) & (NW - 1)) * 64; e0 < n; e0 += NW * 64) {
+        const int e = e0 + lane;
+        const int ec = e < n ? e : 0;
+        const ItemPos<true> row(ec, items);                              // element = row * items + item
+        const int rr = ROWS == 1 ? 0 : (int)row.t1 + (int)row.t2;
+        const ItemPos<GEOM> ip(ROWS == 1 ? ec : row.p, lout);
+        const int p = ip.p;
+        float* const dst = out + ip.times(COUT * lout) + (ROW0 + rr) * lout + p;
+        float acc = bt[(ROW0 + rr) * lout + p];
+        const float4* w = w4 + rr * KS;
+        if (CIN == 1) {
+            const float* x = in + ip.times(lin) + 2 * p - 1;
+            const float4 wk = w[0];
+            float b0 = x[0];
+            b0 = p == 0 ? 0.0f : b0;
+            acc = fmaf(wk.x, b0, acc);
+            acc = fmaf(wk.y, x[1], acc);
+            acc = fmaf(wk.z, x[2], acc);
+            acc = fmaf(wk.w, 0.0f, acc);                                 // the fourth slot of the k-step: zero times zero
+        } else {
+            const float* base = in + ip.times(CIN * lin) + 2 * p - 1;
+#pragma unroll
+            for (int tap = 0; tap < 3; ++tap) {
+                __builtin_amdgcn_sched_barrier(0);                       // a tap's operands at a time: the chain is serial anyway
+#pragma unroll
+                for (int cs = 0; cs < CS; ++cs) {
+                    const float4 wk = w[tap * CS + cs];
+                    float b[4];
+#pragma unroll
+                    for (int s = 0; s < 4; ++s) {
+                        b[s] = base[min(4 * cs + s, CIN - 1) * lin + tap];
+                        if (tap == 0) b[s] = p == 0 ? 0.0f : b[s];
+                    }
+                    acc = fmaf(wk.x, b[0], acc);
+                    acc = fmaf(wk.y, b[1], acc);
+                    acc = fmaf(wk.z, b[2], acc);
+                    acc = fmaf(wk.w, b[3], acc);
+                }
+            }
+        }
+        *dst = fmaxf(acc, 0.0f);
+    }
+}
 // ---- bf16 variants (BASELINE config 3): conv inputs and weights rounded to bf16, fp32 accumulate, on
 // v_mfma_f32_16x16x32_bf16.  One k-step = 32 K slots = channels 8 q + j (q = lane >> 4, j = 0..7) of one tap, so a
 // 17-channel level needs 3 k-steps instead of 15; activations stay fp32 in LDS and are rounded when the B fragment is built.
@@ -258,36 +367,47 @@ __device__ __forceinline__ void mconv_up_bf16(const void* afrag, const float* bt
 // Item = (t, input position i):  out[2i]   = sum_c w[c][o][1] x[c][i]
 //                                out[2i+1] = sum_c w[c][o][2] x[c][i] + w[c][o][0] x[c][i+1]
 // afrag: [MTILES=2][3 tap sets: k=1, k=2, k=0][KSU][64]; K order = part-major (a, then skip), channels in fours.
-template <int NW, bool SKIP, int MT, int COUT = kHidden>
+// TILES: as for mconv_down (kTilesLiveRows: channel 16 is rows_up's).
+template <int NW, bool SKIP, int MT, int COUT = kHidden, int TILES = 0>
 __device__ __forceinline__ void mconv_up(const float* afrag, const float* bt, const float* a,
                                          const float* skip, float* out, float* trash, int l, int tt, int wv, int lane) {
+    constexpr bool LIVE = (TILES & kTilesLiveRows) != 0, GEOM = (TILES & kTilesLaneGeom) != 0;
     constexpr int CS = 5;                      // ceil(17 / 4)
     constexpr int KSU = SKIP ? 2 * CS : CS;
-    constexpr int MTILES = (COUT + 15) / 16, MG = MTILES / MT;
+    constexpr int MTILES = LIVE ? COUT / 16 : (COUT + 15) / 16, MG = MTILES / MT;
+    constexpr int RT = COUT % 16 ? cell_rowtab_floats(COUT % 16, 3 * KSU) : 0;
+    constexpr int CROWS = LIVE ? MTILES * 16 : COUT;
+    static_assert(MTILES % MT == 0, "row tiles in whole groups");
     const int lo = 2 * l, items = tt * l, ntiles = (items + 15) >> 4;
     const int q = lane >> 4, jl = lane & 15;
     for (int tile = wv; tile < ntiles * MG; tile += NW) {
-        const int nt = tile % ntiles, mt0 = (tile / ntiles) * MT;
+        const int nt = GEOM && MG == 1 ? tile : tile % ntiles, mt0 = GEOM && MG == 1 ? 0 : (tile / ntiles) * MT;
         const int item = nt * 16 + jl;
         const bool valid = item < items;
         const int itc = valid ? item : 0;
-        const int t = itc / l, i = itc - t * l;
+        const ItemPos<GEOM> ip(itc, l);
+        const int i = ip.p;
         const bool has_next = i + 1 < l;
+        float* const dst = out + ip.times(COUT * lo) + 2 * i;            // (taken here: the selects behind times() end with the prologue)
+        const int soff = ip.times(kHidden * l) + i;
         f32x4 ev[MT], od[MT];
 #pragma unroll
         for (int mi = 0; mi < MT; ++mi)
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
-                const int o = min((mt0 + mi) * 16 + q * 4 + r, COUT - 1);
+                const int o = LIVE ? (mt0 + mi) * 16 + q * 4 + r : min((mt0 + mi) * 16 + q * 4 + r, COUT - 1);
                 const float2 bb = *reinterpret_cast<const float2*>(bt + o * lo + 2 * i);
                 ev[mi][r] = bb.x;
                 od[mi][r] = bb.y;
             }
         const float* af = afrag + (size_t)mt0 * 3 * KSU * 64 + lane;
+        int tail[MT];                                                    // the partial row tile's fragments lie behind the row table
+#pragma unroll
+        for (int mi = 0; mi < MT; ++mi) tail[mi] = RT != 0 && mt0 + mi == COUT / 16 ? RT : 0;
 #pragma unroll
         for (int part = 0; part < (SKIP ? 2 : 1); ++part) {
             // all operands of one part (a, then skip) are requested before its first MFMA (see mconv_down)
-            const float* src = (part == 0 ? a : skip) + (size_t)t * kHidden * l + i;
+            const float* src = (part == 0 ? a : skip) + soff;
             float x0[CS], x1[CS], av[MT][3][CS];
 #pragma unroll
             for (int cs = 0; cs < CS; ++cs) {
@@ -301,7 +421,7 @@ __device__ __forceinline__ void mconv_up(const float* afrag, const float* bt, co
 #pragma unroll
                 for (int set = 0; set < 3; ++set)
 #pragma unroll
-                    for (int cs = 0; cs < CS; ++cs) av[mi][set][cs] = af[((size_t)(mi * 3 + set) * KSU + part * CS + cs) * 64];
+                    for (int cs = 0; cs < CS; ++cs) av[mi][set][cs] = af[((size_t)(mi * 3 + set) * KSU + part * CS + cs) * 64 + tail[mi]];
             __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
             for (int cs = 0; cs < CS; ++cs)
@@ -314,7 +434,59 @@ __device__ __forceinline__ void mconv_up(const float* afrag, const float* bt, co
         }
 #pragma unroll
         for (int mi = 0; mi < MT; ++mi)
-            store_rows2<COUT>(ev[mi], od[mi], out + (size_t)t * COUT * lo + 2 * i, lo, mt0 + mi, q, trash);
+            store_rows2<CROWS>(ev[mi], od[mi], dst, lo, mt0 + mi, q, trash);
+    }
+}
+
+// Channel 16 of a decoder level (kTilesLiveRows): one lane per item (t, input position i), the two fmaf chains of the accumulator elements
+// ev[16][item] and od[16][item] of mconv_up in its K order -- parts, then channels in fours; od takes the four k=2 slots of a k-step on x[i], then
+// its four k=0 slots on x[i+1] -- from the same bias entries (see rows_down).  rowtab: [KSU][3 tap sets] float4.
+template <int NW, bool SKIP, bool GEOM>
+__device__ __forceinline__ void rows_up(const float* rowtab, const float* bt, const float* a, const float* skip, float* out, int l, int tt,
+                                        int wv, int lane, int w0) {
+    static_assert((NW & (NW - 1)) == 0, "waves are dealt modulo a power of two");
+    constexpr int CS = 5, ROW0 = kHidden - 1;
+    const int lo = 2 * l, items = tt * l;
+    const float4* w4 = reinterpret_cast<const float4*>(rowtab);
+    for (int e0 = ((wv - w0) & (NW - 1)) * 64; e0 < items; e0 += NW * 64) {
+        const int e = e0 + lane;
+        const ItemPos<GEOM> ip(e < items ? e : 0, l);
+        const int i = ip.p;
+        const bool has_next = i + 1 < l;
+        float* const dst = out + ip.times(kHidden * lo) + ROW0 * lo + 2 * i;   // (taken here: the selects behind times() end with the prologue)
+        const int soff = ip.times(kHidden * l) + i;
+        const float2 bb = *reinterpret_cast<const float2*>(bt + ROW0 * lo + 2 * i);
+        float ev = bb.x, od = bb.y;
+#pragma unroll
+        for (int part = 0; part < (SKIP ? 2 : 1); ++part) {
+            const float* src = (part == 0 ? a : skip) + soff;
+            __builtin_amdgcn_sched_barrier(0);                           // a part's operands at a time: the chains are serial anyway
+#pragma unroll
+            for (int cs = 0; cs < CS; ++cs) {
+                const float4 we = w4[(part * CS + cs) * 3], wo = w4[(part * CS + cs) * 3 + 1], wn = w4[(part * CS + cs) * 3 + 2];
+                float x0[4], x1[4];
+#pragma unroll
+                for (int s = 0; s < 4; ++s) {
+                    const int c = min(4 * cs + s, kHidden - 1);
+                    x0[s] = src[c * l];
+                    const float xn = src[c * l + 1];
+                    x1[s] = has_next ? xn : 0.0f;
+                }
+                ev = fmaf(we.x, x0[0], ev);
+                ev = fmaf(we.y, x0[1], ev);
+                ev = fmaf(we.z, x0[2], ev);
+                ev = fmaf(we.w, x0[3], ev);
+                od = fmaf(wo.x, x0[0], od);
+                od = fmaf(wo.y, x0[1], od);
+                od = fmaf(wo.z, x0[2], od);
+                od = fmaf(wo.w, x0[3], od);
+                od = fmaf(wn.x, x1[0], od);
+                od = fmaf(wn.y, x1[1], od);
+                od = fmaf(wn.z, x1[2], od);
+                od = fmaf(wn.w, x1[3], od);
+            }
+        }
+        *reinterpret_cast<float2*>(dst) = make_float2(fmaxf(ev, 0.0f), fmaxf(od, 0.0f));
     }
 }
 
@@ -387,7 +559,7 @@ constexpr int kCellActFloats = 8 + 3 * 16 * kMaxC + 3 * 17 * 14 * kMaxC * 2 + 3 
 // thread has level L+1's share of fragments in flight from L2 and drops it into the other buffer before the barrier.  The
 // levels are a strictly serial chain of short phases (~1 us each): with the fragments fetched at the head of every phase the
 // kernel spent 71 % of its time in s_waitcnt (profiles/r01_v4_pmc_sq.txt); staged, a phase starts on LDS-resident operands.
-constexpr int kCellWFloats = 4096;               // largest level: 51 -> 4 row tiles x 15 k-steps x 64 = 3840 (= 2 x 3 x 10 x 64 of a skip decoder level), in whole rounds
+constexpr int kCellWFloats = 4096;               // largest level: 51 -> 4 row tiles x 15 k-steps x 64 = 3840 (= 2 x 3 x 10 x 64 of a skip decoder level) + its VALU row table (192 / 128), in whole rounds; with live rows only: 3 x 960 + 180 = 3060
 constexpr int kCellBFloats = 768;                // largest bias table: 17 channels x 8C positions = 680 at C = 5, in whole rounds
 constexpr int kCellLdsFloats = kCellActFloats + 2 * kCellWFloats + 2 * kCellBFloats;
 constexpr int kCellSmem = 4 * kCellLdsFloats;
@@ -445,12 +617,14 @@ constexpr bool kCellStageDefault = false;
 constexpr bool kCellStageDefault = true;
 #endif
 constexpr int kCellSmemUnstaged = 4 * kCellActFloats;
-template <int NW, bool BF16 = false, int CT = 0, bool STAGE = kCellStageDefault>
+template <int NW, bool BF16 = false, int CT = 0, bool STAGE = kCellStageDefault, int TILES = DN_CELL_TILES>
 __device__ __forceinline__ void cell_body(char* smem, const CellDev& cd, const float* __restrict__ x,
                                           const float* __restrict__ hx_in, float* __restrict__ out,
                                           float* __restrict__ hx_out, int T, int C_rt, size_t b, int tid,
                                           float hx_scale = 1.0f) {
     constexpr int kCellThreads = NW * 64;
+    constexpr int FT = BF16 ? 0 : TILES;                 // the fp32 tile functions' variant (a bf16 forward only compiles them)
+    constexpr bool LIVE = (FT & kTilesLiveRows) != 0, GEOM = (FT & kTilesLaneGeom) != 0;
     const int C = CT ? CT : C_rt;
     float* lds = reinterpret_cast<float*>(smem);
     const int lane = tid & 63;
@@ -467,16 +641,18 @@ __device__ __forceinline__ void cell_body(char* smem, const CellDev& cd, const f
     auto level = [&](int i) -> CellLevel {
         CellLevel lv;
         if (i < 4) {
-            const int mt = i == 3 ? 4 : 2, ks32 = i == 0 ? 1 : 15, ks16 = i == 0 ? 1 : 3;
+            const int mt = i == 3 ? 4 : 2, ks32 = i == 0 ? 1 : 15, ks16 = i == 0 ? 1 : 3, rows = i == 3 ? 3 : 1;
             lv.w = BF16 ? static_cast<const float*>(cd.wb_down[i]) : cd.w_down[i];
-            lv.wn = BF16 ? mt * ks16 * 64 * 4 : mt * ks32 * 64;
+            // fp32: [whole row tiles][row table][the partial row tile]; the live-row tiles end with the table's last weight
+            lv.wn = BF16 ? mt * ks16 * 64 * 4 : LIVE ? (mt - 1) * ks32 * 64 + rows * ks32 * 4 : mt * ks32 * 64 + cell_rowtab_floats(rows, ks32);
             lv.b = cd.bt_down[i];
             lv.bn = (i == 3 ? kGates : kHidden) * (8 * C >> i);
         } else {
             const int l = i - 4, parts = l == 0 ? 1 : 2;
             const bool bf = BF16 && l < 3;                        // the single-channel last level stays fp32
             lv.w = bf ? static_cast<const float*>(cd.wb_up[l]) : cd.w_up[l];
-            lv.wn = bf ? 2 * 3 * parts * 64 * 4 : l == 3 ? 2 * kHidden * 4 : 2 * 3 * parts * 5 * 64;
+            lv.wn = bf ? 2 * 3 * parts * 64 * 4 : l == 3 ? 2 * kHidden * 4
+                  : LIVE ? 3 * parts * 5 * 64 + 3 * parts * 5 * 4 : 2 * 3 * parts * 5 * 64 + cell_rowtab_floats(1, 3 * parts * 5);
             lv.b = cd.bt_up[l];
             lv.bn = (l == 3 ? 1 : kHidden) * (2 * C << l);
         }
@@ -492,6 +668,8 @@ __device__ __forceinline__ void cell_body(char* smem, const CellDev& cd, const f
 #define DN_LB(i) (STAGE ? static_cast<const float*>(bbuf[(i) & 1]) : level(i).b)
     DN_STG_ISSUE(stgA, 0);
     DN_STG_ISSUE(stgB, 1);
+    // the wave that the round-robin deal of a level's `items` x `mg` MFMA tiles would give the next tile: it takes the level's VALU rows
+    auto next_wave = [](int items, int mg) { return (((items + 15) >> 4) * mg) & (NW - 1); };
 
     DN_CSTAMP(0);
     if (tid < 8) lds[tid] = 0.0f;
@@ -552,14 +730,20 @@ __device__ __forceinline__ void cell_body(char* smem, const CellDev& cd, const f
         // ---- encoder, batched over the chunk (gruunet2.py:136-144); level i multiplies out of buffer i & 1
         DN_STG_ISSUE(stgA, 2);
         if (BF16) mconv_down_bf16<NW, 1, kHidden, 2>(DN_LW(0), DN_LB(0), sx, sd0, trash, 8 * C, tt, wv, lane);
-        else mconv_down<NW, 1, kHidden, 2>(DN_LW(0), DN_LB(0), sx, sd0, trash, 8 * C, tt, wv, lane);
+        else {
+            mconv_down<NW, 1, kHidden, LIVE ? 1 : 2, FT>(DN_LW(0), DN_LB(0), sx, sd0, trash, 8 * C, tt, wv, lane);
+            if constexpr (LIVE) rows_down<NW, 1, kHidden, GEOM>(DN_LW(0) + 64, DN_LB(0), sx, sd0, 8 * C, tt, wv, lane, next_wave(tt * 8 * C, 1));
+        }
         DN_STG_COMMIT(stgB, 1);
         DN_LDS_BARRIER();
         DN_CSTAMP(2);
         DN_STG_ISSUE(stgB, 3);
         DN_CSTAMP(17);
         if (BF16) mconv_down_bf16<NW, kHidden, kHidden, 2>(DN_LW(1), DN_LB(1), sd0, sd1, trash, 4 * C, tt, wv, lane);
-        else mconv_down<NW, kHidden, kHidden, 2>(DN_LW(1), DN_LB(1), sd0, sd1, trash, 4 * C, tt, wv, lane);
+        else {
+            mconv_down<NW, kHidden, kHidden, LIVE ? 1 : 2, FT>(DN_LW(1), DN_LB(1), sd0, sd1, trash, 4 * C, tt, wv, lane);
+            if constexpr (LIVE) rows_down<NW, kHidden, kHidden, GEOM>(DN_LW(1) + 15 * 64, DN_LB(1), sd0, sd1, 4 * C, tt, wv, lane, next_wave(tt * 4 * C, 1));
+        }
         DN_CSTAMP(20);
         DN_STG_COMMIT(stgA, 2);
         DN_CSTAMP(21);
@@ -567,12 +751,18 @@ __device__ __forceinline__ void cell_body(char* smem, const CellDev& cd, const f
         DN_CSTAMP(3);
         DN_STG_ISSUE(stgA, 4);
         if (BF16) mconv_down_bf16<NW, kHidden, kHidden, 1>(DN_LW(2), DN_LB(2), sd1, sd2, trash, 2 * C, tt, wv, lane);
-        else mconv_down<NW, kHidden, kHidden, 1>(DN_LW(2), DN_LB(2), sd1, sd2, trash, 2 * C, tt, wv, lane);
+        else {
+            mconv_down<NW, kHidden, kHidden, 1, FT>(DN_LW(2), DN_LB(2), sd1, sd2, trash, 2 * C, tt, wv, lane);
+            if constexpr (LIVE) rows_down<NW, kHidden, kHidden, GEOM>(DN_LW(2) + 15 * 64, DN_LB(2), sd1, sd2, 2 * C, tt, wv, lane, next_wave(tt * 2 * C, 1));
+        }
         DN_STG_COMMIT(stgB, 3);
         DN_LDS_BARRIER();
         DN_CSTAMP(4);
         if (BF16) mconv_down_bf16<NW, kHidden, kGates, 1>(DN_LW(3), DN_LB(3), sd2, sd3, trash, C, tt, wv, lane);
-        else mconv_down<NW, kHidden, kGates, 1>(DN_LW(3), DN_LB(3), sd2, sd3, trash, C, tt, wv, lane);
+        else {
+            mconv_down<NW, kHidden, kGates, 1, FT>(DN_LW(3), DN_LB(3), sd2, sd3, trash, C, tt, wv, lane);
+            if constexpr (LIVE) rows_down<NW, kHidden, kGates, GEOM>(DN_LW(3) + 3 * 15 * 64, DN_LB(3), sd2, sd3, C, tt, wv, lane, next_wave(tt * C, 3));
+        }
         DN_STG_COMMIT(stgA, 4);
         DN_LDS_BARRIER();
         DN_CSTAMP(5);
@@ -623,20 +813,29 @@ __device__ __forceinline__ void cell_body(char* smem, const CellDev& cd, const f
         // ---- decoder, batched over the chunk (gruunet2.py:184-199); skips are d2, d1, d0 (the last level has no cat)
         DN_STG_ISSUE(stgA, 6);
         if (BF16) mconv_up_bf16<NW, false, 1>(DN_LW(4), DN_LB(4), shi, nullptr, su0, trash, C, tt, wv, lane);
-        else mconv_up<NW, false, 1>(DN_LW(4), DN_LB(4), shi, nullptr, su0, trash, C, tt, wv, lane);
+        else {
+            mconv_up<NW, false, 1, kHidden, FT>(DN_LW(4), DN_LB(4), shi, nullptr, su0, trash, C, tt, wv, lane);
+            if constexpr (LIVE) rows_up<NW, false, GEOM>(DN_LW(4) + 3 * 5 * 64, DN_LB(4), shi, nullptr, su0, C, tt, wv, lane, next_wave(tt * C, 1));
+        }
         DN_STG_COMMIT(stgB, 5);      // requested four phases ago (buffer 1 has been free since the last encoder level)
         DN_STG_ISSUE(stgB, 7);
         DN_LDS_BARRIER();
         DN_CSTAMP(9);
         if (BF16) mconv_up_bf16<NW, true, 1>(DN_LW(5), DN_LB(5), su0, sd2, su1, trash, 2 * C, tt, wv, lane);
-        else mconv_up<NW, true, 1>(DN_LW(5), DN_LB(5), su0, sd2, su1, trash, 2 * C, tt, wv, lane);
+        else {
+            mconv_up<NW, true, 1, kHidden, FT>(DN_LW(5), DN_LB(5), su0, sd2, su1, trash, 2 * C, tt, wv, lane);
+            if constexpr (LIVE) rows_up<NW, true, GEOM>(DN_LW(5) + 3 * 10 * 64, DN_LB(5), su0, sd2, su1, 2 * C, tt, wv, lane, next_wave(tt * 2 * C, 1));
+        }
         DN_STG_COMMIT(stgA, 6);
         DN_LDS_BARRIER();
         DN_CSTAMP(10);
         const bool more = t0 + kCellChunk < T;
         if (more) DN_STG_ISSUE(stgA, 0);
         if (BF16) mconv_up_bf16<NW, true, 2>(DN_LW(6), DN_LB(6), su1, sd1, su2, trash, 4 * C, tt, wv, lane);
-        else mconv_up<NW, true, 2>(DN_LW(6), DN_LB(6), su1, sd1, su2, trash, 4 * C, tt, wv, lane);
+        else {
+            mconv_up<NW, true, LIVE ? 1 : 2, kHidden, FT>(DN_LW(6), DN_LB(6), su1, sd1, su2, trash, 4 * C, tt, wv, lane);
+            if constexpr (LIVE) rows_up<NW, true, GEOM>(DN_LW(6) + 3 * 10 * 64, DN_LB(6), su1, sd1, su2, 4 * C, tt, wv, lane, next_wave(tt * 4 * C, 1));
+        }
         DN_STG_COMMIT(stgB, 7);
         DN_LDS_BARRIER();
         DN_CSTAMP(11);

@@ -438,7 +438,7 @@ __global__ __launch_bounds__(kHopPipeThreads, NFFT == 1536 ? 2 : 1) void frame_k
     stft_body<NFFT, false, true, kHopPipeThreads, PHIN>(smem, d, frames_in, nullptr, a.mel, a.peak, DN_PEAK_NORMALIZE | DN_PRE_WINDOW, b, tid,
                                                         reinterpret_cast<float2*>(a.phas));   // P1-P6
     __syncthreads();
-    cell_body<kHopPipeThreads / 64, BF16, CT>(smem, cd, a.mel, a.hx, a.diff, a.hx, 3, a.C, b, tid);                                      // P7
+    cell_body<kHopPipeThreads / 64, BF16, CT, kCellStageDefault, DN_FRAME_TILES>(smem, cd, a.mel, a.hx, a.diff, a.hx, 3, a.C, b, tid);     // P7
     __syncthreads();
     if (tid >= kHopThreads) return;
     const v2f* init = reinterpret_cast<const v2f*>(PHIN ? a.phas : a.init);

@@ -110,6 +110,9 @@ constexpr int kInvBand = 16;      // diagonals of (fb^T fb)^-1 kept on either si
 constexpr int kSlotMeta = 16;     // u32 of per-stream hand-over data in a pipe's scratch slot (dn_hop.hip: SlotLayout)
 constexpr int kGlwAutoStreams = 768;
 constexpr long kSplitAutoChains = 4096;         // DN_SPLIT_AUTO: chain wavefronts per launch from which a hop goes out as two launches (measured: 2,048 -2.4 %, 4,096 +2.1 %, 8,192 +5.1 %)   // DN_GL_AUTO: from this many streams per pipe on (three per CU of an MI355X; measured crossover between 512 and 768) the back half runs a wavefront per stream
+// Floats of the VALU-row weight table of a GRUUNet2 conv level (CellDev; dn_cell_body.hpp: rows_down / rows_up): `slots4` float4 of weights for each
+// of the `rows` rows of the partial last row tile, in whole 256-byte lines.  It sits between the whole row tiles' fragments and the partial one's.
+constexpr int cell_rowtab_floats(int rows, int slots4) { return (rows * slots4 * 4 + 63) / 64 * 64; }
 constexpr int kArenaSlack = 8192; // zero bytes behind every device arena: kernels that move whole rounds of an array read past its end (dn_cell_body.hpp)
 
 void launch_stft(const DspDev& d, const float* frames, float* spec, float* mel, float* peak, int B, uint32_t flags,
@@ -124,6 +127,8 @@ void launch_synthesis(const DspDev& d, const float* x, const float* diff, const 
                       const float* scale, float* wave, int B, int n_iter, float momentum, hipStream_t st);
 void launch_cell(const CellDev& c, const float* x, const float* hx_in, float* out, float* hx_out, int B, int T,
                  int C, hipStream_t st);
+void launch_cell_parent_tiles(const CellDev& c, const float* x, const float* hx_in, float* out, float* hx_out, int B, int T,
+                              int C, hipStream_t st);
 // Device-resident control block of a dn_pipe.  Every launch of hop_kernel derives its scratch slot, the Griffin-Lim seed
 // and whether a hop is pending from it, and its last workgroup advances it -- so a launch captured in a hipGraph can
 // be replayed indefinitely (nothing that changes from hop to hop is baked into the kernel arguments).
@@ -263,3 +268,9 @@ void launch_server_rows(const DspDev& d, const float* logmel, const float* model
 void launch_istft_general(const DspDev& d, const float* spec, float* wave, int B, int T, hipStream_t st);
 
 }  // namespace dn
+
+// Comparison entry (dn_api_model.hip): the stand-alone fp32 forward on the conv tiles of before the live-row / lane-geometry change.  Not in the
+// public header; nothing in the product calls it.
+struct dn_model;
+extern "C" int dn_cell_forward_parent_tiles(const dn_model* m, const float* x, const float* hx_in, float* out, float* hx_out, int32_t B, int32_t T,
+                                            int32_t F, int32_t C, void* stream);

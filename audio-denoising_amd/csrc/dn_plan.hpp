@@ -45,6 +45,9 @@ struct CellDev {
     //   w_down[l]: [m-tile][k-step][64]          K = taps x channels-in-fours (level 0: the 3 taps)
     //   w_up[l<3]: [m-tile][tap set][k-step][64]  tap sets k=1 (even outputs), k=2 and k=0 (odd outputs)
     //   w_up[3]  : the single-output-channel last level runs on the VALU: [part: a, skip][17][4] = w[k=1], w[k=2], w[k=0], 0
+    // In front of the last, partial m-tile (channel 16; rows 48..50 of the 51-row encoder level) lies the same rows' table for the VALU lanes that
+    // compute them (dn_cell_body.hpp: rows_down / rows_up), cell_rowtab_floats() floats: [row][k-step] float4 / [k-step][tap set] float4 = the
+    // weights of the k-step's four K slots.  The live-row tiles stage [whole m-tiles][table] and never read the partial m-tile.
     const float* w_down[4];  // data channels 1,17,17,17 -> 17,17,17,51
     const float* w_gh;       // [m-tile 4][k-step 13][64]  hidden-gate conv fragments, K slot = 3 c + tap (held in VGPRs across time steps)
     const float* w_up[4];    // data channels 17,34,34,34 -> 17,17,17,1

@@ -70,7 +70,7 @@ __global__ __launch_bounds__(kHopPipeThreads, NFFT == 1536 ? 2 : 1) void sess_fr
     float2* phas = PHIN ? reinterpret_cast<float2*>(const_cast<float*>(a.init)) + i * 3 * kBins : nullptr;
     stft_body<NFFT, false, true, kHopPipeThreads, PHIN>(smem, d, ring, nullptr, mel, peak, DN_PEAK_NORMALIZE | DN_PRE_WINDOW, 0, tid, phas);   // P1-P6
     __syncthreads();
-    cell_body<kHopPipeThreads / 64, BF16, CT>(smem, cd, mel, hx, diff, hx, 3, a.C, 0, tid);                                      // P7
+    cell_body<kHopPipeThreads / 64, BF16, CT, kCellStageDefault, DN_FRAME_TILES>(smem, cd, mel, hx, diff, hx, 3, a.C, 0, tid);     // P7
     __syncthreads();
     if (tid >= kHopThreads) return;
     const v2f* init = PHIN ? reinterpret_cast<const v2f*>(phas) : a.init != nullptr ? reinterpret_cast<const v2f*>(a.init) + i * 3 * kBins : nullptr;
