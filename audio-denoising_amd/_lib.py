@@ -31,6 +31,8 @@ SYMBOLS = (
     "dn_sessions_get_counters", "dn_sessions_record_bytes", "dn_sessions_export", "dn_sessions_import",
     "dn_clip_workspace_bytes", "dn_clip_process",
     "dn_stft_phasors", "dn_workspace_bytes_ex", "dn_clip_workspace_bytes_ex",
+    "dn_griffinlim_general_whole_max", "dn_griffinlim_general_workspace_bytes", "dn_griffinlim_general", "dn_griffinlim_draw_phases_general",
+    "dn_server_mag",
 )
 
 DN_PEAK_NORMALIZE = 1
@@ -43,7 +45,9 @@ DN_SPLIT_AUTO, DN_SPLIT_OFF, DN_SPLIT_ON = -1, 0, 1
 DN_SESS_AUTO, DN_SESS_ONE_LAUNCH, DN_SESS_TWO_LAUNCHES = 0, 1, 2
 DN_CLIP_GL_PER_COLUMN, DN_CLIP_GL_PER_STREAM = 2, 4
 DN_PHASE_FROM_INPUT = 8
-ABI_VERSION = 8
+DN_GLG_WHOLE, DN_GLG_STEPS = 2, 4
+DN_GL_INIT_NORMALIZE = 16
+ABI_VERSION = 9
 
 
 class ModelCfg(C.Structure):
@@ -154,6 +158,13 @@ class DnLib:
         L.dn_workspace_bytes_ex.restype = C.c_size_t
         L.dn_clip_workspace_bytes_ex.argtypes = [vp, i32, i32, u32]
         L.dn_clip_workspace_bytes_ex.restype = C.c_size_t
+        L.dn_griffinlim_general_whole_max.argtypes = [vp]
+        L.dn_griffinlim_general_whole_max.restype = i32
+        L.dn_griffinlim_general_workspace_bytes.argtypes = [vp, i32, i32]
+        L.dn_griffinlim_general_workspace_bytes.restype = C.c_size_t
+        L.dn_griffinlim_general.argtypes = [vp, p, p, u64, u64, p, vp, i32, i32, i32, f32, u32, vp]
+        L.dn_griffinlim_draw_phases_general.argtypes = [vp, u64, u64, p, i32, i32, vp]
+        L.dn_server_mag.argtypes = [vp, p, p, p, i32, vp]
         if L.dn_abi_version() != ABI_VERSION:
             raise ImportError(f"{path}: ABI version {L.dn_abi_version()} != {ABI_VERSION}; rebuild the extension")
 

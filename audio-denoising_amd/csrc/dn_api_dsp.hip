@@ -220,6 +220,8 @@ int check_dsp_args(const char* who, const dn_dsp* d, bool pointers, bool need_me
     return DN_OK;
 }
 
+constexpr long long kGlgMaxRows = 1ll << 22;          // B x T of one dn_griffinlim_general call: every grid and 32-bit index stays in range
+
 int refuse_init_angles(const char* who) { return fail(DN_ERR_INVALID, std::string(who) + ": DN_PHASE_FROM_INPUT takes the phases from the input: init_angles must be NULL"); }
 
 // The workspace of dn_process_frame / dn_stream_step, in floats: mel [B][3][M] | residual [B][3][M] | linear magnitude [B][3][K] | peak [B], then (each
@@ -424,6 +426,55 @@ int dn_istft_general(const dn_dsp* d, const float* spec, float* wave, int32_t B,
     if (B < 0 || T < 2) return fail(DN_ERR_INVALID, "dn_istft_general: need B >= 0 and at least 2 columns");
     dn::launch_istft_general(d->view, spec, wave, B, T, as_stream(stream));
     return check_launch("istft_general_kernel");
+}
+
+// ---- Griffin-Lim on any number of columns.  The workspace is the caller's: X | prev ([B][T][K] complex each) | the rebuilt signal [B][hop (T - 1)]
+int32_t dn_griffinlim_general_whole_max(const dn_dsp* d) { return d ? dn::kGlgWholeMax : 0; }
+
+size_t dn_griffinlim_general_workspace_bytes(const dn_dsp* d, int32_t B, int32_t T) {
+    if (!d || B <= 0 || T < 3 || (long long)B * T > kGlgMaxRows) return 0;
+    const size_t rows = (size_t)B * (size_t)T, K = (size_t)d->cfg.n_fft / 2 + 1;
+    return ((2 * rows * K * 2 + (size_t)B * (size_t)(T - 1) * (d->cfg.n_fft / 2)) * sizeof(float) + 255) & ~size_t(255);
+}
+
+int dn_griffinlim_general(const dn_dsp* d, const float* mag, const float* init_angles, uint64_t seed, uint64_t stream_id0, float* wave,
+                          void* workspace, int32_t B, int32_t T, int32_t n_iter, float momentum, uint32_t flags, void* stream) {
+    if (B == 0) return DN_OK;
+    DN_TRY(check_dsp_args("dn_griffinlim_general", d, mag && wave && workspace, false, B >= 0 && n_iter >= 0, "size"));
+    if (T < 3) return fail(DN_ERR_INVALID, "dn_griffinlim_general: needs at least 3 columns (reflect padding needs hop*(T-1) > n_fft/2, as torch.stft)");
+    if ((long long)B * T > kGlgMaxRows) return fail(DN_ERR_INVALID, "dn_griffinlim_general: B x T exceeds " + std::to_string(kGlgMaxRows) + " columns a call");
+    dn::GlgArgs a{};
+    DN_TRY(check_momentum(momentum, &a.mom));
+    if (flags & ~(uint32_t)(DN_GLG_WHOLE | DN_GLG_STEPS | DN_GL_INIT_NORMALIZE)) return fail(DN_ERR_INVALID, "dn_griffinlim_general: unknown flag bits");
+    const uint32_t form = flags & (uint32_t)(DN_GLG_WHOLE | DN_GLG_STEPS);
+    if (form == (uint32_t)(DN_GLG_WHOLE | DN_GLG_STEPS)) return fail(DN_ERR_INVALID, "dn_griffinlim_general: DN_GLG_WHOLE and DN_GLG_STEPS exclude each other");
+    if ((flags & DN_GL_INIT_NORMALIZE) && !init_angles) return fail(DN_ERR_INVALID, "dn_griffinlim_general: DN_GL_INIT_NORMALIZE needs init_angles (the spectrum to take the phases from)");
+    if ((form & DN_GLG_WHOLE) && T > dn::kGlgWholeMax)
+        return fail(DN_ERR_UNSUPPORTED, "dn_griffinlim_general: DN_GLG_WHOLE holds at most " + std::to_string(dn::kGlgWholeMax) + " columns on chip (got " + std::to_string(T) + ")");
+    const size_t rows = (size_t)B * (size_t)T, K = (size_t)d->cfg.n_fft / 2 + 1;
+    a.mag = mag; a.init = init_angles; a.normalize = (flags & DN_GL_INIT_NORMALIZE) != 0; a.seed = seed; a.sid0 = stream_id0; a.wave = wave;
+    a.x = static_cast<float*>(workspace); a.prev = a.x + rows * K * 2; a.sig = a.prev + rows * K * 2;
+    a.B = B; a.T = T; a.n_iter = n_iter;
+    if (form == DN_GLG_STEPS || (form == 0 && T > dn::kGlgWholeMax)) {
+        dn::launch_glg_steps(d->view, a, as_stream(stream));
+        return check_launch("glg_step_kernel");
+    }
+    dn::launch_glg_whole(d->view, a, as_stream(stream));
+    return check_launch("glg_whole_kernel");
+}
+
+int dn_griffinlim_draw_phases_general(const dn_dsp* d, uint64_t seed, uint64_t stream_id0, float* angles_out, int32_t B, int32_t T, void* stream) {
+    if (B == 0) return DN_OK;
+    DN_TRY(check_dsp_args("dn_griffinlim_draw_phases_general", d, angles_out != nullptr, false, B >= 0 && T >= 1 && (long long)B * T <= kGlgMaxRows, "size"));
+    dn::launch_draw_phases_general(d->view, angles_out, seed, stream_id0, B, T, as_stream(stream));
+    return check_launch("glg_draw_kernel");
+}
+
+int dn_server_mag(const dn_dsp* d, const float* logmel, const float* model_out, float* mag_out, int32_t rows, void* stream) {
+    if (rows == 0) return DN_OK;
+    DN_TRY(check_dsp_args("dn_server_mag", d, logmel && model_out && mag_out, true, rows >= 0, "size"));
+    dn::launch_server_mag(d->view, logmel, model_out, mag_out, rows, as_stream(stream));
+    return check_launch("server_rows_kernel<magnitude>");
 }
 
 // ---- the whole hop in one launch

@@ -70,7 +70,8 @@ __global__ __launch_bounds__(64) void stft_general_kernel(DspDev d, const float*
 
 // One workgroup (192 threads) per (b,t) row: mel magnitude exp(log_mel - 3 relu(out)) - 1  ->  pinv contraction, relu
 // -> times the unit phasor of the noisy bin (torch.polar(O, spec.angle()); angle(0) = 0).
-template <int NFFT>
+// POLAR = false (dn_server_mag): the magnitude alone, [rows][K] float through `spec_out`, for a Griffin-Lim behind it; spec_in is not read.
+template <int NFFT, bool POLAR = true>
 __global__ __launch_bounds__(kInvThreads) void server_rows_kernel(DspDev d, const float* __restrict__ logmel,
                                                                   const float* __restrict__ model_out,
                                                                   const float2* spec_in, float2* spec_out) {      // may alias (in-place): no __restrict__
@@ -101,6 +102,10 @@ __global__ __launch_bounds__(kInvThreads) void server_rows_kernel(DspDev d, cons
         const int k = tid + kInvThreads * r;
         if (k < kBins) {
             const float mag = fmaxf(acc[r], 0.0f);                              // InverseMelScale's relu
+            if (!POLAR) {
+                reinterpret_cast<float*>(spec_out)[row * kBins + k] = mag;
+                continue;
+            }
             const float2 z = spec_in[row * kBins + k];
             const float h = hypotf(z.x, z.y);
             const float2 u = h > 0.0f ? make_float2(z.x / h, z.y / h) : make_float2(1.0f, 0.0f);
@@ -171,6 +176,14 @@ void launch_server_rows(const DspDev& d, const float* logmel, const float* model
     if (d.n_fft == 1536) hipLaunchKernelGGL(server_rows_kernel<1536>, dim3(rows), dim3(kInvThreads), 0, st, d, logmel, model_out, si, so);
     else if (d.n_fft == 512) hipLaunchKernelGGL(server_rows_kernel<512>, dim3(rows), dim3(kInvThreads), 0, st, d, logmel, model_out, si, so);
     else hipLaunchKernelGGL(server_rows_kernel<1024>, dim3(rows), dim3(kInvThreads), 0, st, d, logmel, model_out, si, so);
+}
+
+void launch_server_mag(const DspDev& d, const float* logmel, const float* model_out, float* mag_out, int rows, hipStream_t st) {
+    const float2* si = nullptr;
+    float2* so = reinterpret_cast<float2*>(mag_out);
+    if (d.n_fft == 1536) hipLaunchKernelGGL((server_rows_kernel<1536, false>), dim3(rows), dim3(kInvThreads), 0, st, d, logmel, model_out, si, so);
+    else if (d.n_fft == 512) hipLaunchKernelGGL((server_rows_kernel<512, false>), dim3(rows), dim3(kInvThreads), 0, st, d, logmel, model_out, si, so);
+    else hipLaunchKernelGGL((server_rows_kernel<1024, false>), dim3(rows), dim3(kInvThreads), 0, st, d, logmel, model_out, si, so);
 }
 
 void launch_istft_general(const DspDev& d, const float* spec, float* wave, int B, int T, hipStream_t st) {

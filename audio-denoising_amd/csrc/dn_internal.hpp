@@ -266,6 +266,20 @@ void launch_stft_general(const DspDev& d, const float* x, float* spec, float* lo
 void launch_server_rows(const DspDev& d, const float* logmel, const float* model_out, const float* spec_in, float* spec_out, int rows,
                         hipStream_t st);
 void launch_istft_general(const DspDev& d, const float* spec, float* wave, int B, int T, hipStream_t st);
+void launch_server_mag(const DspDev& d, const float* logmel, const float* model_out, float* mag_out, int rows, hipStream_t st);
+// Griffin-Lim on [B][T][K] magnitudes, any T >= 3 (dn_glg.hip).  WHOLE: one launch, T <= kGlgWholeMax wavefronts a workgroup, x / prev / sig unused.
+// STEPS: x, prev [B][T][K] complex and sig [B][hop (T - 1)] are the caller's workspace.  Both give the same bits.
+constexpr int kGlgWholeMax = 8;
+struct GlgArgs {
+    const float* mag; const float* init; int normalize;           // init: [B][T][K] complex or null = device RNG; normalize: its unit phasors
+    uint64_t seed, sid0;
+    float* wave;                                                   // [B][hop (T - 1)]
+    float* x; float* prev; float* sig;
+    int B, T, n_iter; float mom;                                   // mom = momentum / (1 + momentum)
+};
+void launch_glg_whole(const DspDev& d, const GlgArgs& a, hipStream_t st);
+void launch_glg_steps(const DspDev& d, const GlgArgs& a, hipStream_t st);
+void launch_draw_phases_general(const DspDev& d, float* out, uint64_t seed, uint64_t sid0, int B, int T, hipStream_t st);
 
 }  // namespace dn
 

@@ -225,10 +225,16 @@ class ServerDenoiser:
     """The request-loop body of the reference's socket server (server.py:199-217) for B mono chunks at once:
     STFT -> mel -> log1p -> GRUUNet2 over all T columns -> relu(out)*3, hx*=0.9 -> inverse mel of exp(log_mel-out)-1
     -> torch.polar with the NOISY phase -> ISTFT.  Chunks may have any length L > n_fft/2; the result has
-    hop*(L//hop) samples (InverseSpectrogram with length=None).  Four launches; no CPU fallback."""
+    hop*(L//hop) samples (InverseSpectrogram with length=None).  Four launches; no CPU fallback.
+
+    ``n_iter=k`` (not None) puts phase reconstruction behind the model instead: the inverse-mel magnitude alone (dn_server_mag), then ``k``
+    iterations of Griffin-Lim on the whole chunk (dn_griffinlim_general; chunks need T = 1 + L // hop >= 3 columns).  ``phase="input"`` starts from
+    the phases of the noisy STFT (``n_iter=0`` is then the default path's reconstruction), ``phase="random"`` from the device draw of
+    ``seed + r`` for the object's r-th request.  ``n_iter=None`` (default) is the four launches above, untouched."""
 
     def __init__(self, model: GRUUNet2, sample_rate: int = 48000, n_fft: int = 1024, hop_length: int = 512, n_mels: int = 64,
-                 hx_decay: float = 0.9, device=None, window: torch.Tensor | None = None):
+                 hx_decay: float = 0.9, device=None, window: torch.Tensor | None = None, n_iter: int | None = None, momentum: float = 0.99,
+                 phase: str = "input", seed: int = 0):
         self.device = torch.device(device if device is not None else next(model.parameters()).device)
         if self.device.type != "cuda":
             raise RuntimeError("ServerDenoiser needs a 'cuda' device; there is no CPU path in this package")
@@ -238,6 +244,14 @@ class ServerDenoiser:
         self.n_stft = n_fft // 2 + 1
         fb = melscale_fbanks(self.n_stft, 0.0, float(sample_rate // 2), n_mels, sample_rate)        # server.py:175-176
         self.plan = DspPlan(self.device, sample_rate, n_fft, hop_length, n_mels, fb=fb, window=torch.hann_window(n_fft) if window is None else window)
+        if n_iter is not None and n_iter < 0:
+            raise ValueError("n_iter must be None or >= 0")
+        if not (0 <= momentum < 1):
+            raise ValueError("momentum must be in the range [0, 1). Found: {}".format(momentum))
+        if phase not in ("input", "random"):
+            raise ValueError(f'phase must be "input" or "random"; got {phase!r}')
+        self.n_iter, self.momentum, self.phase, self.seed = n_iter, float(momentum), phase, int(seed)
+        self.requests = 0          # requests served with n_iter set: request r draws from seed + r
 
     def process(self, x: torch.Tensor, hx: torch.Tensor | None = None):
         """x (B, L) float32 on the GPU, hx (B,17,C) or None -> (wave (B, hop*(L//hop)), hx_new)."""
@@ -260,6 +274,16 @@ class ServerDenoiser:
             lib.check(lib.dn_stft_general(plan.handle, x.data_ptr(), spec.data_ptr(), logmel.data_ptr(), B, L, st))
             lib.check(lib.dn_cell_forward_ex(model_h, logmel.data_ptr(), hx0.data_ptr(), out.data_ptr(), hx1.data_ptr(), B, T, self.n_mels, Cb,
                                              self.hx_decay, st))
+            if self.n_iter is not None:
+                mag = torch.empty(B, T, self.n_stft, dtype=torch.float32, device=dev)
+                ws = torch.empty(max(1, int(lib.dn_griffinlim_general_workspace_bytes(plan.handle, B, T))), dtype=torch.uint8, device=dev)
+                lib.check(lib.dn_server_mag(plan.handle, logmel.data_ptr(), out.data_ptr(), mag.data_ptr(), B * T, st))
+                from_input = self.phase == "input"
+                lib.check(lib.dn_griffinlim_general(plan.handle, mag.data_ptr(), spec.data_ptr() if from_input else None, self.seed + self.requests, 0,
+                                                    wave.data_ptr(), ws.data_ptr(), B, T, self.n_iter, self.momentum,
+                                                    _lib.DN_GL_INIT_NORMALIZE if from_input else 0, st))
+                self.requests += 1
+                return wave, hx1
             lib.check(lib.dn_server_rows(plan.handle, logmel.data_ptr(), out.data_ptr(), spec.data_ptr(), spec.data_ptr(), B * T, st))
             lib.check(lib.dn_istft_general(plan.handle, spec.data_ptr(), wave.data_ptr(), B, T, st))
         return wave, hx1

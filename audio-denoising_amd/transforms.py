@@ -135,7 +135,8 @@ def _check_fft_args(n_fft, win_length, hop_length):
 
 class Spectrogram(_PlanModule):
     """Spectrogram(power=None|1|2, center=True, pad_mode='reflect', onesided=True, normalized=False):
-    (.., n_fft) -> (.., n_fft/2+1, 3).  app3.py:135-139,191."""
+    (.., L) -> (.., n_fft/2+1, 1 + L // hop) for any L > n_fft/2 (dn_stft_general); a frame of exactly n_fft samples is the hop path's 3-column
+    dn_stft.  app3.py:135-139,191."""
 
     def __init__(self, n_fft=400, win_length=None, hop_length=None, pad=0, window_fn=torch.hann_window, power=2.0,
                  normalized=False, wkwargs=None, center=True, pad_mode="reflect", onesided=True):
@@ -152,16 +153,21 @@ class Spectrogram(_PlanModule):
 
     def forward(self, waveform: torch.Tensor) -> torch.Tensor:
         _require(waveform, torch.float32, "Spectrogram")
-        if waveform.shape[-1] != self.n_fft:
-            raise NotImplementedError(f"frames of exactly n_fft={self.n_fft} samples (3 STFT columns) are supported; got {waveform.shape[-1]}")
+        L = waveform.shape[-1]
+        if L <= self.n_fft // 2:
+            raise RuntimeError(f"reflect padding needs more than n_fft/2 = {self.n_fft // 2} samples (as torch.stft); got {L}")
+        T = 1 + L // self.hop_length
         lead = waveform.shape[:-1]
-        x = waveform.reshape(-1, self.n_fft).contiguous()
+        x = waveform.reshape(-1, L).contiguous()
         B = x.shape[0]
         plan = self.plan(x.device)
-        spec = torch.empty(B, 3, plan.n_stft, 2, dtype=torch.float32, device=x.device)
+        spec = torch.empty(B, T, plan.n_stft, 2, dtype=torch.float32, device=x.device)
         with torch.cuda.device(x.device):
-            plan.lib.check(plan.lib.dn_stft(plan.handle, x.data_ptr(), spec.data_ptr(), B, 0, _stream_ptr(x.device)))
-        out = torch.view_as_complex(spec).reshape(lead + (3, plan.n_stft)).transpose(-1, -2)
+            if L == self.n_fft:
+                plan.lib.check(plan.lib.dn_stft(plan.handle, x.data_ptr(), spec.data_ptr(), B, 0, _stream_ptr(x.device)))
+            else:
+                plan.lib.check(plan.lib.dn_stft_general(plan.handle, x.data_ptr(), spec.data_ptr(), None, B, L, _stream_ptr(x.device)))
+        out = torch.view_as_complex(spec).reshape(lead + (T, plan.n_stft)).transpose(-1, -2)
         if self.power is None:
             return out
         return out.abs() if self.power == 1.0 else out.abs().pow(self.power)
@@ -243,7 +249,9 @@ class InverseMelScale(_PlanModule):
 
 class GriffinLim(_PlanModule):
     """GriffinLim(n_fft, n_iter=32, win_length, hop_length, window_fn, power=2.0, momentum=0.99, length=None,
-    rand_init=True): (.., n_fft/2+1, 3) magnitude**power -> (.., n_fft).  app3.py:149-153,213.
+    rand_init=True): (.., n_fft/2+1, T) magnitude**power -> (.., hop*(T-1)) for any T >= 3.  T == 3 (one n_fft-sample frame) is the hop path's
+    dn_griffinlim, app3.py:149-153,213; any other T runs dn_griffinlim_general (every iteration on chip up to
+    dn_griffinlim_general_whole_max columns, two launches an iteration beyond; the same samples either way).
 
     ``rand_init=True`` draws the initial phases on the device from a counter-based generator whose
     seed comes from torch's global RNG (so ``torch.manual_seed`` makes runs repeatable); pass
@@ -257,7 +265,8 @@ class GriffinLim(_PlanModule):
             raise ValueError("momentum must be in the range [0, 1). Found: {}".format(momentum))
         self.n_fft, self.win_length, self.hop_length = _check_fft_args(n_fft, win_length, hop_length)
         if length is not None and length != n_fft:
-            raise NotImplementedError("length=None (3 columns -> n_fft samples) is what the hop path uses")
+            raise NotImplementedError("length=None (T columns -> hop*(T-1) samples) is what the kernels produce")
+        self.length = length
         self.n_iter, self.power, self.momentum, self.rand_init = n_iter, power, momentum, rand_init
         window = window_fn(self.win_length) if wkwargs is None else window_fn(self.win_length, **wkwargs)
         self.register_buffer("window", window)
@@ -268,13 +277,16 @@ class GriffinLim(_PlanModule):
     def forward(self, specgram: torch.Tensor, init_angles: torch.Tensor | None = None) -> torch.Tensor:
         _require(specgram, torch.float32, "GriffinLim")
         K = self.n_fft // 2 + 1
-        if specgram.shape[-2] != K or specgram.shape[-1] != 3:
-            raise NotImplementedError(f"expected (.., {K}, 3) (one n_fft-sample frame = 3 columns); got {tuple(specgram.shape)}")
+        T = specgram.shape[-1]
+        if self.length is not None and T != 3:
+            raise NotImplementedError("length=None (T columns -> hop*(T-1) samples) is what the kernels produce")
+        if specgram.shape[-2] != K or T < 3:
+            raise RuntimeError(f"expected (.., {K}, T) with T >= 3 columns (reflect padding needs hop*(T-1) > n_fft/2); got {tuple(specgram.shape)}")
         if self.power != 1.0:
             specgram = specgram.pow(1.0 / self.power)
-        rows = _rows_layout(specgram)                      # [.., 3, K]
+        rows = _rows_layout(specgram)                      # [.., T, K]
         lead = rows.shape[:-2]
-        B = rows.numel() // (3 * K)
+        B = rows.numel() // (T * K)
         plan = self.plan(rows.device)
         ia_ptr, seed = None, 0
         if init_angles is not None:
@@ -289,15 +301,21 @@ class GriffinLim(_PlanModule):
             ia = torch.zeros(rows.shape + (2,), dtype=torch.float32, device=rows.device)
             ia[..., 0] = 1.0
             ia_ptr = ia.data_ptr()
-        wave = torch.empty(lead + (self.n_fft,), dtype=torch.float32, device=rows.device)
+        wave = torch.empty(lead + (self.hop_length * (T - 1),), dtype=torch.float32, device=rows.device)
         with torch.cuda.device(rows.device):
-            plan.lib.check(plan.lib.dn_griffinlim(plan.handle, rows.data_ptr(), ia_ptr, seed, 0, None, wave.data_ptr(), B,
-                                                  int(self.n_iter), float(self.momentum), _stream_ptr(rows.device)))
+            if T == 3:
+                plan.lib.check(plan.lib.dn_griffinlim(plan.handle, rows.data_ptr(), ia_ptr, seed, 0, None, wave.data_ptr(), B,
+                                                      int(self.n_iter), float(self.momentum), _stream_ptr(rows.device)))
+            else:
+                ws = torch.empty(max(1, int(plan.lib.dn_griffinlim_general_workspace_bytes(plan.handle, B, T))), dtype=torch.uint8, device=rows.device)
+                plan.lib.check(plan.lib.dn_griffinlim_general(plan.handle, rows.data_ptr(), ia_ptr, seed, 0, wave.data_ptr(), ws.data_ptr(), B, T,
+                                                              int(self.n_iter), float(self.momentum), 0, _stream_ptr(rows.device)))
         return wave
 
 
 class InverseSpectrogram(_PlanModule):
-    """InverseSpectrogram(n_fft, win_length, hop_length): complex (.., n_fft/2+1, 3) -> (.., n_fft).  server.py:174,216."""
+    """InverseSpectrogram(n_fft, win_length, hop_length): complex (.., n_fft/2+1, T) -> (.., hop*(T-1)) for any T >= 2 (dn_istft_general; 3 columns
+    are the hop path's dn_istft).  server.py:174,216."""
 
     def __init__(self, n_fft=400, win_length=None, hop_length=None, pad=0, window_fn=torch.hann_window, normalized=False,
                  wkwargs=None, center=True, pad_mode="reflect", onesided=True):
@@ -314,13 +332,19 @@ class InverseSpectrogram(_PlanModule):
     def forward(self, spectrogram: torch.Tensor, length=None) -> torch.Tensor:
         _require(spectrogram, torch.complex64, "InverseSpectrogram")
         K = self.n_fft // 2 + 1
-        if spectrogram.shape[-2] != K or spectrogram.shape[-1] != 3 or (length is not None and length != self.n_fft):
-            raise NotImplementedError(f"expected (.., {K}, 3) and length None; got {tuple(spectrogram.shape)}")
-        rows = torch.view_as_real(_rows_layout(spectrogram).resolve_conj()).contiguous()   # [.., 3, K, 2]
+        T = spectrogram.shape[-1]
+        if length is not None and (length != self.n_fft or T != 3):
+            raise NotImplementedError("length=None (T columns -> hop*(T-1) samples) is what the kernels produce")
+        if spectrogram.shape[-2] != K or T < 2:
+            raise RuntimeError(f"expected (.., {K}, T) with T >= 2 columns; got {tuple(spectrogram.shape)}")
+        rows = torch.view_as_real(_rows_layout(spectrogram).resolve_conj()).contiguous()   # [.., T, K, 2]
         lead = rows.shape[:-3]
-        B = rows.numel() // (3 * K * 2)
+        B = rows.numel() // (T * K * 2)
         plan = self.plan(rows.device)
-        wave = torch.empty(lead + (self.n_fft,), dtype=torch.float32, device=rows.device)
+        wave = torch.empty(lead + (self.hop_length * (T - 1),), dtype=torch.float32, device=rows.device)
         with torch.cuda.device(rows.device):
-            plan.lib.check(plan.lib.dn_istft(plan.handle, rows.data_ptr(), wave.data_ptr(), B, _stream_ptr(rows.device)))
+            if T == 3:
+                plan.lib.check(plan.lib.dn_istft(plan.handle, rows.data_ptr(), wave.data_ptr(), B, _stream_ptr(rows.device)))
+            else:
+                plan.lib.check(plan.lib.dn_istft_general(plan.handle, rows.data_ptr(), wave.data_ptr(), B, T, _stream_ptr(rows.device)))
         return wave

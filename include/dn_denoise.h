@@ -56,7 +56,7 @@
 extern "C" {
 #endif
 
-#define DN_ABI_VERSION 8
+#define DN_ABI_VERSION 9
 
 typedef enum dn_status {
     DN_OK = 0,
@@ -214,6 +214,31 @@ int dn_stft_general(const dn_dsp* d, const float* x, float* spec, float* logmel,
 int dn_server_rows(const dn_dsp* d, const float* logmel, const float* model_out, const float* spec_in, float* spec_out,
                    int32_t rows, void* stream);
 int dn_istft_general(const dn_dsp* d, const float* spec, float* wave, int32_t B, int32_t T, void* stream);
+
+/* ---- Griffin-Lim on any number of columns: phase reconstruction for the any-length path -----------------------
+ * dn_griffinlim_general: mag [dev][B][T][K], T >= 3 -> wave [dev][B][hop*(T-1)], torchaudio's fast Griffin-Lim (n_iter iterations, momentum as
+ * torchaudio's, then one istft; n_iter = 0 is istft(init * mag)).  init_angles [dev][B][T][K] complex, or NULL: column t of stream b draws the
+ * Philox phases of (seed, stream_id0 + b, t) -- the numbering of dn_griffinlim, so with T = 3 both draw the same.  DN_GL_INIT_NORMALIZE: init_angles
+ * holds an arbitrary spectrum (the noisy STFT, say) whose unit phasors are the initial phases, with the arithmetic of DN_PHASE_FROM_INPUT.
+ * Two forms that give the same bits: WHOLE, one launch with every iteration on chip, for T <= dn_griffinlim_general_whole_max(d); STEPS, two
+ * launches an iteration, for any T.  With neither force flag WHOLE runs when T fits.  `workspace`: dn_griffinlim_general_workspace_bytes(d, B, T)
+ * bytes of the caller's (nonzero for every valid (B, T), 0 for a null plan or T < 3; WHOLE leaves it unused); the library allocates nothing and
+ * nothing synchronises.  Every argument is checked before the first launch: null d / mag / wave / workspace, B < 0, n_iter < 0, T < 3 (reflect
+ * padding needs hop*(T-1) > n_fft/2), momentum outside [0, 1), unknown flag bits, both force flags, DN_GL_INIT_NORMALIZE with NULL init_angles
+ * (all DN_ERR_INVALID), DN_GLG_WHOLE with T above the maximum (DN_ERR_UNSUPPORTED); the outputs are then untouched.  B == 0 returns DN_OK. */
+#define DN_GLG_WHOLE 2u            /* force; T > dn_griffinlim_general_whole_max(d): DN_ERR_UNSUPPORTED */
+#define DN_GLG_STEPS 4u            /* force; both: DN_ERR_INVALID; neither: WHOLE when T fits */
+#define DN_GL_INIT_NORMALIZE 16u
+int32_t dn_griffinlim_general_whole_max(const dn_dsp* d);
+size_t dn_griffinlim_general_workspace_bytes(const dn_dsp* d, int32_t B, int32_t T);
+int dn_griffinlim_general(const dn_dsp* d, const float* mag, const float* init_angles, uint64_t seed, uint64_t stream_id0,
+                          float* wave, void* workspace, int32_t B, int32_t T, int32_t n_iter, float momentum, uint32_t flags,
+                          void* stream);
+/* The phases dn_griffinlim_general draws with init_angles == NULL: angles_out [dev][B][T][K] complex. */
+int dn_griffinlim_draw_phases_general(const dn_dsp* d, uint64_t seed, uint64_t stream_id0, float* angles_out, int32_t B, int32_t T,
+                                      void* stream);
+/* The magnitude half of dn_server_rows: relu(pinv . (exp(logmel - 3 relu(model_out)) - 1)) -> mag_out [dev][rows][K] float. */
+int dn_server_mag(const dn_dsp* d, const float* logmel, const float* model_out, float* mag_out, int32_t rows, void* stream);
 
 /* flags of the fused entry points */
 #define DN_CONV_BF16 1u /* BASELINE config 3: encoder/decoder convs on bf16 MFMA tiles (as dn_cell_forward_bf16); 0 = exact fp32 */
