@@ -8,6 +8,7 @@
 //   istft_general_kernel  InverseSpectrogram (length=None)                  server.py:216       two waves per output hop
 // GRUUNet2 itself is the ordinary dn_cell_forward (any T), with the `hx = hx * 0.9` of server.py:214 folded into
 // the state write-back (dn_cell_forward_ex).
+#include "dn_dispatch.hpp"
 #include "dn_invmel_body.hpp"
 #include "dn_stft_body.hpp"
 
@@ -164,33 +165,29 @@ __global__ __launch_bounds__(128) void istft_general_kernel(DspDev d, const floa
 void launch_stft_general(const DspDev& d, const float* x, float* spec, float* logmel, int B, int L, hipStream_t st) {
     const int T = 1 + L / (d.n_fft / 2);
     float2* sp = reinterpret_cast<float2*>(spec);
-    if (d.n_fft == 1536) hipLaunchKernelGGL(stft_general_kernel<1536>, dim3(B * T), dim3(64), 0, st, d, x, L, T, sp, logmel);
-    else if (d.n_fft == 512) hipLaunchKernelGGL(stft_general_kernel<512>, dim3(B * T), dim3(64), 0, st, d, x, L, T, sp, logmel);
-    else hipLaunchKernelGGL(stft_general_kernel<1024>, dim3(B * T), dim3(64), 0, st, d, x, L, T, sp, logmel);
+    with_nfft(d.n_fft, [&](auto n) { hipLaunchKernelGGL(stft_general_kernel<decltype(n)::value>, dim3(B * T), dim3(64), 0, st, d, x, L, T, sp, logmel); });
 }
 
 void launch_server_rows(const DspDev& d, const float* logmel, const float* model_out, const float* spec_in, float* spec_out, int rows,
                         hipStream_t st) {
     const float2* si = reinterpret_cast<const float2*>(spec_in);
     float2* so = reinterpret_cast<float2*>(spec_out);
-    if (d.n_fft == 1536) hipLaunchKernelGGL(server_rows_kernel<1536>, dim3(rows), dim3(kInvThreads), 0, st, d, logmel, model_out, si, so);
-    else if (d.n_fft == 512) hipLaunchKernelGGL(server_rows_kernel<512>, dim3(rows), dim3(kInvThreads), 0, st, d, logmel, model_out, si, so);
-    else hipLaunchKernelGGL(server_rows_kernel<1024>, dim3(rows), dim3(kInvThreads), 0, st, d, logmel, model_out, si, so);
+    with_nfft(d.n_fft, [&](auto n) {
+        hipLaunchKernelGGL(server_rows_kernel<decltype(n)::value>, dim3(rows), dim3(kInvThreads), 0, st, d, logmel, model_out, si, so);
+    });
 }
 
 void launch_server_mag(const DspDev& d, const float* logmel, const float* model_out, float* mag_out, int rows, hipStream_t st) {
     const float2* si = nullptr;
     float2* so = reinterpret_cast<float2*>(mag_out);
-    if (d.n_fft == 1536) hipLaunchKernelGGL((server_rows_kernel<1536, false>), dim3(rows), dim3(kInvThreads), 0, st, d, logmel, model_out, si, so);
-    else if (d.n_fft == 512) hipLaunchKernelGGL((server_rows_kernel<512, false>), dim3(rows), dim3(kInvThreads), 0, st, d, logmel, model_out, si, so);
-    else hipLaunchKernelGGL((server_rows_kernel<1024, false>), dim3(rows), dim3(kInvThreads), 0, st, d, logmel, model_out, si, so);
+    with_nfft(d.n_fft, [&](auto n) {
+        hipLaunchKernelGGL((server_rows_kernel<decltype(n)::value, false>), dim3(rows), dim3(kInvThreads), 0, st, d, logmel, model_out, si, so);
+    });
 }
 
 void launch_istft_general(const DspDev& d, const float* spec, float* wave, int B, int T, hipStream_t st) {
     const float2* sp = reinterpret_cast<const float2*>(spec);
-    if (d.n_fft == 1536) hipLaunchKernelGGL(istft_general_kernel<1536>, dim3(B * (T - 1)), dim3(128), 0, st, d, sp, T, wave);
-    else if (d.n_fft == 512) hipLaunchKernelGGL(istft_general_kernel<512>, dim3(B * (T - 1)), dim3(128), 0, st, d, sp, T, wave);
-    else hipLaunchKernelGGL(istft_general_kernel<1024>, dim3(B * (T - 1)), dim3(128), 0, st, d, sp, T, wave);
+    with_nfft(d.n_fft, [&](auto n) { hipLaunchKernelGGL(istft_general_kernel<decltype(n)::value>, dim3(B * (T - 1)), dim3(128), 0, st, d, sp, T, wave); });
 }
 
 }  // namespace dn

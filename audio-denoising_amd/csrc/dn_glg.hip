@@ -23,6 +23,7 @@
 //   t = 0,     n < hop:   s[hop - n]            n = 0 reads s[hop], the first sample of block 1
 //   t = T - 1, n >= hop:  s[L - 2 - (n - hop)]  n = 2 hop - 1 reads s[(T - 2) hop - 1], the last sample of block T - 3
 // With T = 3 both land in blocks 0 and 1.  T >= 3 is what keeps every index in range (hop (T - 1) > n_fft / 2, torch.stft's own condition).
+#include "dn_dispatch.hpp"
 #include "dn_gl_body.hpp"
 #include "dn_stft_body.hpp"
 
@@ -297,9 +298,7 @@ static GlgInit glg_init_of(const GlgArgs& a) { return GlgInit{reinterpret_cast<c
 void launch_glg_whole(const DspDev& d, const GlgArgs& a, hipStream_t st) {
     const GlgInit gi = glg_init_of(a);
     const dim3 grid(a.B), block(64 * a.T);
-    if (d.n_fft == 1536) hipLaunchKernelGGL(glg_whole_kernel<1536>, grid, block, 0, st, d, a.mag, gi, a.wave, a.T, a.n_iter, a.mom);
-    else if (d.n_fft == 512) hipLaunchKernelGGL(glg_whole_kernel<512>, grid, block, 0, st, d, a.mag, gi, a.wave, a.T, a.n_iter, a.mom);
-    else hipLaunchKernelGGL(glg_whole_kernel<1024>, grid, block, 0, st, d, a.mag, gi, a.wave, a.T, a.n_iter, a.mom);
+    with_nfft(d.n_fft, [&](auto n) { hipLaunchKernelGGL(glg_whole_kernel<decltype(n)::value>, grid, block, 0, st, d, a.mag, gi, a.wave, a.T, a.n_iter, a.mom); });
 }
 
 void launch_glg_steps(const DspDev& d, const GlgArgs& a, hipStream_t st) {
@@ -307,15 +306,14 @@ void launch_glg_steps(const DspDev& d, const GlgArgs& a, hipStream_t st) {
     const dim3 grid(a.B * a.T), block(64);
     v2f* x = reinterpret_cast<v2f*>(a.x);
     v2f* prev = reinterpret_cast<v2f*>(a.prev);
-    if (d.n_fft == 1536) hipLaunchKernelGGL(glg_init_kernel<1536>, grid, block, 0, st, a.mag, gi, a.T, x, prev);
-    else if (d.n_fft == 512) hipLaunchKernelGGL(glg_init_kernel<512>, grid, block, 0, st, a.mag, gi, a.T, x, prev);
-    else hipLaunchKernelGGL(glg_init_kernel<1024>, grid, block, 0, st, a.mag, gi, a.T, x, prev);
-    for (int it = 0; it < a.n_iter; ++it) {
-        launch_istft_general(d, reinterpret_cast<const float*>(a.x), a.sig, a.B, a.T, st);
-        if (d.n_fft == 1536) hipLaunchKernelGGL(glg_step_kernel<1536>, grid, block, 0, st, d, a.mag, (const float*)a.sig, a.T, x, prev, a.mom);
-        else if (d.n_fft == 512) hipLaunchKernelGGL(glg_step_kernel<512>, grid, block, 0, st, d, a.mag, (const float*)a.sig, a.T, x, prev, a.mom);
-        else hipLaunchKernelGGL(glg_step_kernel<1024>, grid, block, 0, st, d, a.mag, (const float*)a.sig, a.T, x, prev, a.mom);
-    }
+    with_nfft(d.n_fft, [&](auto n) {
+        constexpr int kN = decltype(n)::value;
+        hipLaunchKernelGGL(glg_init_kernel<kN>, grid, block, 0, st, a.mag, gi, a.T, x, prev);
+        for (int it = 0; it < a.n_iter; ++it) {
+            launch_istft_general(d, reinterpret_cast<const float*>(a.x), a.sig, a.B, a.T, st);
+            hipLaunchKernelGGL(glg_step_kernel<kN>, grid, block, 0, st, d, a.mag, (const float*)a.sig, a.T, x, prev, a.mom);
+        }
+    });
     launch_istft_general(d, reinterpret_cast<const float*>(a.x), a.wave, a.B, a.T, st);
 }
 

@@ -14,6 +14,7 @@
 //   HBM       : magnitudes in (3*513 floats), waveform out (1024 floats).  That is all.
 // One __syncthreads per iteration (overlap-add hand-off between the three columns); every
 // FFT-internal exchange is wave-private.
+#include "dn_dispatch.hpp"
 #include "dn_gl_body.hpp"
 
 namespace dn {
@@ -32,12 +33,10 @@ void launch_griffinlim(const DspDev& d, const float* mag, const float* init, uin
                        const float* scale, float* wave, int B, int n_iter, float momentum, hipStream_t st) {
     const float mom = momentum / (1.0f + momentum);
     const v2f* ia = reinterpret_cast<const v2f*>(init);
-    if (d.n_fft == 1536)
-        hipLaunchKernelGGL((griffinlim_kernel<1536, false>), dim3(B), dim3(kGlThreads), 0, st, d, mag, (const float*)nullptr, ia, seed, sid0, scale, wave, n_iter, mom);
-    else if (d.n_fft == 512)
-        hipLaunchKernelGGL((griffinlim_kernel<512, false>), dim3(B), dim3(kGlThreads), 0, st, d, mag, (const float*)nullptr, ia, seed, sid0, scale, wave, n_iter, mom);
-    else
-        hipLaunchKernelGGL((griffinlim_kernel<1024, false>), dim3(B), dim3(kGlThreads), 0, st, d, mag, (const float*)nullptr, ia, seed, sid0, scale, wave, n_iter, mom);
+    with_nfft(d.n_fft, [&](auto n) {
+        hipLaunchKernelGGL((griffinlim_kernel<decltype(n)::value, false>), dim3(B), dim3(kGlThreads), 0, st, d, mag, (const float*)nullptr, ia, seed, sid0, scale,
+                           wave, n_iter, mom);
+    });
 }
 
 // The initial phases a Griffin-Lim launch with init_angles == NULL draws for (seed, stream_id0 + stream): [B][3][K] complex, real and imaginary
@@ -63,12 +62,9 @@ void launch_synthesis(const DspDev& d, const float* x, const float* diff, const 
                       const float* scale, float* wave, int B, int n_iter, float momentum, hipStream_t st) {
     const float mom = momentum / (1.0f + momentum);
     const v2f* ia = reinterpret_cast<const v2f*>(init);
-    if (d.n_fft == 1536)
-        hipLaunchKernelGGL((griffinlim_kernel<1536, true>), dim3(B), dim3(kGlThreads), 0, st, d, x, diff, ia, seed, sid0, scale, wave, n_iter, mom);
-    else if (d.n_fft == 512)
-        hipLaunchKernelGGL((griffinlim_kernel<512, true>), dim3(B), dim3(kGlThreads), 0, st, d, x, diff, ia, seed, sid0, scale, wave, n_iter, mom);
-    else
-        hipLaunchKernelGGL((griffinlim_kernel<1024, true>), dim3(B), dim3(kGlThreads), 0, st, d, x, diff, ia, seed, sid0, scale, wave, n_iter, mom);
+    with_nfft(d.n_fft, [&](auto n) {
+        hipLaunchKernelGGL((griffinlim_kernel<decltype(n)::value, true>), dim3(B), dim3(kGlThreads), 0, st, d, x, diff, ia, seed, sid0, scale, wave, n_iter, mom);
+    });
 }
 
 }  // namespace dn

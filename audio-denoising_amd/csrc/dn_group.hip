@@ -1,4 +1,5 @@
 // dn_group.hip -- hop groups: H consecutive hops of every stream in ONE launch, every Griffin-Lim chain whole (dn_pipe_set_group).
+#include "dn_dispatch.hpp"
 #include "dn_hop_common.hpp"
 
 namespace dn {
@@ -210,18 +211,13 @@ __global__ __launch_bounds__(kHopPipeThreads, 2) void group_kernel(DspDev d, con
 }
 
 void launch_group(const DspDev& d, const CellDev& c, const HopArgs& a, bool bf16, hipStream_t st) {
-    const dim3 grid(a.back_blocks + a.front_B), block(kHopPipeThreads);
-    const bool stream = a.ola != nullptr, usual = a.C == 5;
-    auto go = [&](auto k) { hipLaunchKernelGGL(k, grid, block, 0, st, d, a.d_dev, a.c_dev, a); };
-    auto pick = [&](auto stream_c, auto phin_c) {
-        constexpr bool S = decltype(stream_c)::value, P = decltype(phin_c)::value;
-        if (usual) { if (bf16) go(group_kernel<1024, S, true, 5, P>); else go(group_kernel<1024, S, false, 5, P>); }
-        else { if (bf16) go(group_kernel<1024, S, true, 0, P>); else go(group_kernel<1024, S, false, 0, P>); }
-    };
-    using T = std::true_type; using F = std::false_type;
-    const bool phin = a.phase_in && a.front_B > 0;          // (a flush runs no analysis: the default instantiation)
-    if (stream) { if (phin) pick(T{}, T{}); else pick(T{}, F{}); }
-    else { if (phin) pick(F{}, T{}); else pick(F{}, F{}); }
+    // (PHIN only with front workgroups: a flush runs no analysis and takes the default instantiation)
+    with_bool(a.ola != nullptr, a.phase_in && a.front_B > 0, [&](auto stream, auto phin) {
+        with_model<1024>(bf16, a.C, [&](auto bf, auto ct) {
+            hipLaunchKernelGGL((group_kernel<1024, decltype(stream)::value, decltype(bf)::value, decltype(ct)::value, decltype(phin)::value>),
+                               dim3(a.back_blocks + a.front_B), dim3(kHopPipeThreads), 0, st, d, a.d_dev, a.c_dev, a);
+        });
+    });
 }
 
 }  // namespace dn

@@ -9,6 +9,7 @@
 // A workgroup handles kRows = 3 rows (the three columns of one stream): the mel rows sit in
 // LDS and are broadcast; each lane owns output bins k, k+192, ... and streams the transposed
 // pseudo-inverse ([M][K'], coalesced over k, L2-resident) exactly once for all three rows.
+#include "dn_dispatch.hpp"
 #include "dn_invmel_body.hpp"
 
 namespace dn {
@@ -21,19 +22,13 @@ __global__ __launch_bounds__(kInvThreads) void invmel_kernel(DspDev d, const flo
     invmel_body<NFFT, RESIDUAL>(smem, d, x, diff, lin, rows, (size_t)blockIdx.x * kInvRows, threadIdx.x);
 }
 
-template <int NFFT>
-static void launch_invmel_n(const DspDev& d, const float* x, const float* diff, float* lin, int rows, hipStream_t st) {
-    dim3 grid((rows + kInvRows - 1) / kInvRows), block(kInvThreads);
-    if (diff != nullptr)
-        hipLaunchKernelGGL((invmel_kernel<NFFT, true>), grid, block, 0, st, d, x, diff, lin, rows);
-    else
-        hipLaunchKernelGGL((invmel_kernel<NFFT, false>), grid, block, 0, st, d, x, diff, lin, rows);
-}
-
 void launch_invmel(const DspDev& d, const float* x, const float* diff, float* lin, int rows, hipStream_t st) {
-    if (d.n_fft == 1536) launch_invmel_n<1536>(d, x, diff, lin, rows, st);
-    else if (d.n_fft == 512) launch_invmel_n<512>(d, x, diff, lin, rows, st);
-    else launch_invmel_n<1024>(d, x, diff, lin, rows, st);
+    with_nfft(d.n_fft, [&](auto n) {
+        with_bool(diff != nullptr, [&](auto residual) {
+            hipLaunchKernelGGL((invmel_kernel<decltype(n)::value, decltype(residual)::value>), dim3((rows + kInvRows - 1) / kInvRows), dim3(kInvThreads),
+                               0, st, d, x, diff, lin, rows);
+        });
+    });
 }
 
 }  // namespace dn

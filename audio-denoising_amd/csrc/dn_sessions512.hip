@@ -1,3 +1,10 @@
-// n_fft 512 one-launch form of the session pool under the default scheduling strategy (Makefile; see dn_sessions.hip)
-#define DN_SESS_TU_512 1
-#include "dn_sessions.hip"
+// n_fft 512 one-launch form of the session pool under the default scheduling strategy (Makefile; see dn_sess_kernels.hpp)
+#include "dn_sess_kernels.hpp"
+
+namespace dn {
+
+void launch_sess_frame_unit(Size<512>, const DspDev& d, const CellDev& c, const SessArgs& a, bool bf16, hipStream_t st, bool phase_in) {
+    launch_sess_frame_of<512>(d, c, a, bf16, st, phase_in);
+}
+
+}  // namespace dn

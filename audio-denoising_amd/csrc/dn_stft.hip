@@ -5,6 +5,7 @@
 // reflect-padded n_fft-sample input produces.  The frame is read from HBM once (float4,
 // coalesced), lives in LDS, and only the 3 x n_mels log-mel values (or the 3 x 513 complex
 // bins for the plain Spectrogram entry point) go back to HBM.
+#include "dn_dispatch.hpp"
 #include "dn_stft_body.hpp"
 
 namespace dn {
@@ -40,32 +41,24 @@ __global__ __launch_bounds__(64) void mel_kernel(DspDev d, const float* __restri
     }
 }
 
-template <int NFFT>
-static void launch_stft_n(const DspDev& d, const float* frames, float* spec, float* mel, float* peak, int B, uint32_t flags,
-                          hipStream_t st) {
-    dim3 grid(B), block(kStftThreads);
-    float2* sp = reinterpret_cast<float2*>(spec);
-    if (spec != nullptr && mel != nullptr)
-        hipLaunchKernelGGL((stft_kernel<NFFT, true, true>), grid, block, 0, st, d, frames, sp, mel, peak, flags);
-    else if (spec != nullptr)
-        hipLaunchKernelGGL((stft_kernel<NFFT, true, false>), grid, block, 0, st, d, frames, sp, mel, peak, flags);
-    else
-        hipLaunchKernelGGL((stft_kernel<NFFT, false, true>), grid, block, 0, st, d, frames, sp, mel, peak, flags);
-}
-
 void launch_stft(const DspDev& d, const float* frames, float* spec, float* mel, float* peak, int B, uint32_t flags,
                  hipStream_t st) {
-    if (d.n_fft == 1536) launch_stft_n<1536>(d, frames, spec, mel, peak, B, flags, st);
-    else if (d.n_fft == 512) launch_stft_n<512>(d, frames, spec, mel, peak, B, flags, st);
-    else launch_stft_n<1024>(d, frames, spec, mel, peak, B, flags, st);
+    float2* sp = reinterpret_cast<float2*>(spec);
+    with_nfft(d.n_fft, [&](auto n) {
+        constexpr int kN = decltype(n)::value;
+        auto go = [&](auto k) { hipLaunchKernelGGL(k, dim3(B), dim3(kStftThreads), 0, st, d, frames, sp, mel, peak, flags); };
+        // (spectrum, mel or both: three of the four instantiations exist)
+        if (spec != nullptr && mel != nullptr) go(stft_kernel<kN, true, true>);
+        else if (spec != nullptr) go(stft_kernel<kN, true, false>);
+        else go(stft_kernel<kN, false, true>);
+    });
 }
 
 void launch_stft_phasors(const DspDev& d, const float* frames, float* phas, int B, uint32_t flags, hipStream_t st) {
-    const dim3 grid(B), block(kStftThreads);
     float2* ph = reinterpret_cast<float2*>(phas);
-    if (d.n_fft == 1536) hipLaunchKernelGGL(stft_phasor_kernel<1536>, grid, block, 0, st, d, frames, ph, flags);
-    else if (d.n_fft == 512) hipLaunchKernelGGL(stft_phasor_kernel<512>, grid, block, 0, st, d, frames, ph, flags);
-    else hipLaunchKernelGGL(stft_phasor_kernel<1024>, grid, block, 0, st, d, frames, ph, flags);
+    with_nfft(d.n_fft, [&](auto n) {
+        hipLaunchKernelGGL(stft_phasor_kernel<decltype(n)::value>, dim3(B), dim3(kStftThreads), 0, st, d, frames, ph, flags);
+    });
 }
 
 void launch_mel(const DspDev& d, const float* mag, float* mel, int rows, hipStream_t st) {

@@ -379,7 +379,8 @@ HOP_N_ITER = 1
 HOP_GEOMETRIES = [(n_fft, n_mels) for n_fft in (512, 1024, 1536) for n_mels in (80, 32)]
 HOP_SAMPLE_RATE = {512: 16000, 1024: 16000, 1536: 48000}
 CHAIN_HOPS, CHAIN_GROUP = 4, 3
-CHAIN_PATHS = ("group", "split", "sessions", "clip")
+CHAIN_PATHS = ("group", "split", "sessions", "clip",
+               "sessions_two_launches")          # (the pool's other schedule: its front kernel picks its own (bf16, C) instantiation)
 
 
 def hop_params(n_fft, n_mels):
