@@ -29,7 +29,7 @@ SYMBOLS = (
     "dn_momo_forward", "dn_last_error", "dn_abi_version",
     "dn_sessions_create", "dn_sessions_destroy", "dn_sessions_open", "dn_sessions_close", "dn_sessions_push", "dn_sessions_set_schedule",
     "dn_sessions_get_counters", "dn_sessions_record_bytes", "dn_sessions_export", "dn_sessions_import",
-    "dn_clip_workspace_bytes", "dn_clip_process",
+    "dn_clip_workspace_bytes", "dn_clip_process", "dn_clip_ragged_workspace_bytes", "dn_clip_process_ragged",
     "dn_stft_phasors", "dn_workspace_bytes_ex", "dn_clip_workspace_bytes_ex",
     "dn_griffinlim_general_whole_max", "dn_griffinlim_general_workspace_bytes", "dn_griffinlim_general", "dn_griffinlim_draw_phases_general",
     "dn_server_mag",
@@ -153,6 +153,9 @@ class DnLib:
         L.dn_clip_workspace_bytes.argtypes = [vp, i32, i32]
         L.dn_clip_workspace_bytes.restype = C.c_size_t
         L.dn_clip_process.argtypes = [vp, vp, p, i32, p, p, p, p, i32, p, u64, u64, i32, f32, vp, i32, i32, u32, vp]
+        L.dn_clip_ragged_workspace_bytes.argtypes = [vp, i32, i64, u32]
+        L.dn_clip_ragged_workspace_bytes.restype = C.c_size_t
+        L.dn_clip_process_ragged.argtypes = [vp, vp, p, i32, p, p, p, p, i32, p, u64, u64, p, p, i32, f32, vp, i32, u32, vp]
         L.dn_stft_phasors.argtypes = [vp, p, p, i32, u32, vp]
         L.dn_workspace_bytes_ex.argtypes = [vp, i32, u32]
         L.dn_workspace_bytes_ex.restype = C.c_size_t

@@ -556,4 +556,69 @@ int dn_clip_process(const dn_model* m, const dn_dsp* d, const void* hops_in, int
     return check_launch("dn_clip_process");
 }
 
+// ---- ragged: stream b runs n_hops[b] hops.  The table -- off [B + 1] int32 (to an 8-byte boundary), frame0 [B] uint64 -- heads the workspace, rounded
+// up to 256 bytes; the uniform call's layout for F = sum n_hops frames follows
+static size_t clip_table_bytes(int32_t B) {
+    const size_t off = ((size_t)B + 1) * sizeof(int32_t);
+    return ((((off + 7) & ~size_t(7)) + (size_t)B * sizeof(uint64_t)) + 255) & ~size_t(255);
+}
+
+size_t dn_clip_ragged_workspace_bytes(const dn_dsp* d, int32_t B, int64_t total_hops, uint32_t flags) {
+    if (B < 1 || total_hops < 1 || total_hops > kClipMaxFrames) return 0;
+    const size_t rows = dn_clip_workspace_bytes_ex(d, 1, (int32_t)total_hops, flags);          // (0: a null plan, one without mel stages, unknown flag bits)
+    return rows == 0 ? 0 : clip_table_bytes(B) + rows;
+}
+
+int dn_clip_process_ragged(const dn_model* m, const dn_dsp* d, const void* hops_in, int32_t in_s16, float* ring, float* ola, float* hx, void* hops_out, int32_t out_s16,
+                           const float* init_angles, uint64_t seed, uint64_t stream_id0, const int32_t* n_hops, const uint64_t* frame0, int32_t n_iter, float momentum,
+                           void* workspace, int32_t B, uint32_t flags, void* stream) {
+    // every argument is validated before the table is copied and the first kernel launched, so a failed call leaves ring, ola, hx, hops_out and the
+    // workspace untouched
+    if (B < 1) return fail(DN_ERR_INVALID, "dn_clip_process_ragged: needs B >= 1 streams");
+    if (!n_hops) return fail(DN_ERR_INVALID, "dn_clip_process_ragged: null n_hops");
+    long long F = 0;
+    for (int32_t b = 0; b < B; ++b) {
+        if (n_hops[b] < 0) return fail(DN_ERR_INVALID, "dn_clip_process_ragged: n_hops[" + std::to_string(b) + "] is negative");
+        F += n_hops[b];
+    }
+    if (F > kClipMaxFrames) return fail(DN_ERR_INVALID, "dn_clip_process_ragged: sum n_hops exceeds " + std::to_string(kClipMaxFrames) + " frames a call (tile the clips)");
+    const uint32_t gl = flags & (uint32_t)(DN_CLIP_GL_PER_COLUMN | DN_CLIP_GL_PER_STREAM);
+    dn::ClipArgs a{};
+    DN_TRY(check_hop_args("dn_clip_process_ragged", m, d, B, n_iter, momentum, flags & ~gl, &a.mom));
+    if (gl == (uint32_t)(DN_CLIP_GL_PER_COLUMN | DN_CLIP_GL_PER_STREAM)) return fail(DN_ERR_INVALID, "dn_clip_process_ragged: DN_CLIP_GL_PER_COLUMN and DN_CLIP_GL_PER_STREAM exclude each other");
+    if ((gl & DN_CLIP_GL_PER_STREAM) && d->cfg.n_fft != 1024) return refuse_not_1024("the wavefront-per-stream Griffin-Lim is built");
+    if ((flags & DN_PHASE_FROM_INPUT) && init_angles) return refuse_init_angles("dn_clip_process_ragged");
+    if (F == 0) return DN_OK;          // no stream has a hop: nothing is enqueued
+    if (!hops_in || !ring || !ola || !hx || !hops_out || !workspace) return fail(DN_ERR_INVALID, "dn_clip_process_ragged: null argument");
+    const int M = d->cfg.n_mels, C = M / 16;
+    const BiasSet* bs = nullptr;
+    DN_TRY(build_bias(m, C, &bs));
+    // the table, built in a vector of the library's own (the caller's arrays are free again when the call returns) and copied in stream order to
+    // the head of the workspace: the source is pageable, so the copy has left it when hipMemcpyAsync returns
+    const size_t off_bytes = ((((size_t)B + 1) * sizeof(int32_t)) + 7) & ~size_t(7), table = off_bytes + (size_t)B * sizeof(uint64_t);
+    thread_local std::vector<uint64_t> host;          // (kept from call to call: no allocation once it has grown)
+    host.assign(table / sizeof(uint64_t), 0);
+    int32_t* off = reinterpret_cast<int32_t*>(host.data());
+    uint64_t* f0 = host.data() + off_bytes / sizeof(uint64_t);
+    off[0] = 0;
+    for (int32_t b = 0; b < B; ++b) {
+        off[b + 1] = off[b] + n_hops[b];
+        f0[b] = frame0 ? frame0[b] : 0;
+    }
+    DN_HIP(hipMemcpyAsync(workspace, host.data(), table, hipMemcpyHostToDevice, as_stream(stream)));
+    char* rows = static_cast<char*>(workspace) + clip_table_bytes(B);
+    a.off = static_cast<const int*>(workspace);
+    a.frame0 = reinterpret_cast<const uint64_t*>(static_cast<const char*>(workspace) + off_bytes);
+    a.hops_in = hops_in; a.in_s16 = in_s16 != 0; a.ring = ring; a.ola = ola; a.hx = hx; a.hops_out = hops_out; a.out_s16 = out_s16 != 0;
+    a.init = init_angles; a.seed = seed; a.sid0 = stream_id0; a.n_iter = n_iter;
+    a.C = C; a.B = B; a.N = 0; a.n_fft = d->cfg.n_fft; a.n_mels = M;
+    a.frames = (size_t)F;
+    a.fr = reinterpret_cast<float*>(rows); a.fr_stride = clip_row_floats(d);
+    a.mel = a.fr + a.frames * a.fr_stride; a.diff = a.mel + a.frames * 3 * M; a.peak = a.diff + a.frames * 3 * M;
+    if (flags & DN_PHASE_FROM_INPUT) a.phas = reinterpret_cast<float*>(rows + dn_clip_workspace_bytes(d, 1, (int32_t)F));
+    a.per_stream = d->cfg.n_fft == 1024 && ((gl & DN_CLIP_GL_PER_STREAM) || (gl == 0 && (long)a.frames >= dn::kClipGlwAutoFrames));
+    dn::launch_clip(d->view, bs->view_dev.get(), a, (flags & DN_CONV_BF16) != 0, as_stream(stream));
+    return check_launch("dn_clip_process_ragged");
+}
+
 }  // extern "C"

@@ -28,14 +28,27 @@ __device__ __forceinline__ void clip_emit(void* out, int s16, size_t at, v2f v) 
         *reinterpret_cast<v2f*>(static_cast<float*>(out) + at) = v;
     }
 }
+// A ragged call (a.off non-null) has one job per frame instead, found from off alone: thread u owns pair u % pairs of frame f = u / pairs, hop i of
+// the stream b that owns f (clip_owner; f differs within a workgroup here, so these loads are per lane).  Frame 0 of a stream is its job 0, frame i
+// in 1 .. N_b - 2 is job i (out_{i+1}), and the stream's last frame idles when N_b > 1.  The jobs themselves are the ones below, N = N_b.
 __global__ __launch_bounds__(kClipFoldThreads) void clip_fold_kernel(ClipArgs a) {
     const int hop = a.n_fft / 2, pairs = hop / 2;
-    const size_t jobs = a.N > 1 ? (size_t)a.N - 1 : 1;
     const size_t u = (size_t)blockIdx.x * kClipFoldThreads + threadIdx.x;
-    if (u >= (size_t)a.B * jobs * pairs) return;
     const int m = (int)(u % pairs);
-    const size_t bj = u / pairs, b = bj / jobs, j = bj - b * jobs;
-    const size_t f0 = b * (size_t)a.N;
+    size_t b, j, f0;
+    int N;
+    if (a.off != nullptr) {
+        const size_t f = u / pairs;
+        if (f >= a.frames) return;
+        const int o = clip_owner(a.off, a.B, (int)f);
+        b = (size_t)o; f0 = (size_t)a.off[o]; j = f - f0; N = a.off[o + 1] - a.off[o];
+        if (j != 0 && j + 1 >= (size_t)N) return;          // the last frame of a stream with more than one
+    } else {
+        const size_t jobs = a.N > 1 ? (size_t)a.N - 1 : 1;
+        if (u >= (size_t)a.B * jobs * pairs) return;
+        const size_t bj = u / pairs;
+        b = bj / jobs; j = bj - b * jobs; f0 = b * (size_t)a.N; N = a.N;
+    }
     const int n = 2 * m;
     auto pair = [&](size_t i, int off) { return *reinterpret_cast<const v2f*>(a.fr + (f0 + i) * a.fr_stride + off + n); };
     auto fma2 = [](v2f e, float s, v2f c) { return mk2(fmaf(e[0], s, c[0]), fmaf(e[1], s, c[1])); };
@@ -47,12 +60,12 @@ __global__ __launch_bounds__(kClipFoldThreads) void clip_fold_kernel(ClipArgs a)
         clip_emit(a.hops_out, a.out_s16, out0, lo);
         const v2f first = fma2(pair(0, 0), a.peak[f0], hi);          // hop 0's frame on the old line
         v2f nlo = first;
-        if (a.N > 1) {
+        if (N > 1) {
             clip_emit(a.hops_out, a.out_s16, out0 + hop, first);
-            const size_t l = (size_t)a.N - 1;
+            const size_t l = (size_t)N - 1;
             nlo = fma2(pair(l, 0), a.peak[f0 + l], fma2(pair(l - 1, hop), a.peak[f0 + l - 1], zero));
         }
-        const size_t l = (size_t)a.N - 1;
+        const size_t l = (size_t)N - 1;
         const v2f nhi = fma2(pair(l, hop), a.peak[f0 + l], zero);
         *reinterpret_cast<v2f*>(orow + n) = nlo;
         *reinterpret_cast<v2f*>(orow + hop + n) = nhi;
@@ -82,7 +95,7 @@ void launch_clip(const DspDev& d, const CellDev* c_dev, const ClipArgs& args, bo
         }
     });
     const size_t jobs = a.N > 1 ? (size_t)a.N - 1 : 1;
-    const size_t units = (size_t)a.B * jobs * (a.n_fft / 4);
+    const size_t units = (a.off != nullptr ? a.frames : (size_t)a.B * jobs) * (a.n_fft / 4);          // ragged: a job per frame
     hipLaunchKernelGGL(clip_fold_kernel, dim3((unsigned)((units + kClipFoldThreads - 1) / kClipFoldThreads)), dim3(kClipFoldThreads), 0, st, a);
 }
 

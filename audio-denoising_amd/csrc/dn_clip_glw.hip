@@ -16,10 +16,10 @@ __global__ __launch_bounds__(kHopPipeThreads, 2) void clip_chain_glw_kernel(DspD
         DN_LDS_BARRIER();
         return;
     }
-    const size_t b = f / (size_t)a.N, i = f - b * (size_t)a.N;
+    const ClipFrame c = clip_frame(a, f);          // (f is the same for the whole wavefront: wv is a readfirstlane)
     float* row = a.fr + f * a.fr_stride;
     const v2f* init = a.init != nullptr ? reinterpret_cast<const v2f*>(a.init) + f * 3 * kBins : nullptr;
-    glw_body<kNR, kEmitStage>(smem, d, row, init, a.seed + i, a.sid0 + b, nullptr, nullptr, a.n_iter, a.mom, 0, lane, wv, nullptr, nullptr, 0, 0, -1,
+    glw_body<kNR, kEmitStage>(smem, d, row, init, c.seed, a.sid0 + c.b, nullptr, nullptr, a.n_iter, a.mom, 0, lane, wv, nullptr, nullptr, 0, 0, -1,
                               kGlwFresh, nullptr, tid);
     // the wave's LDS line -> the frame row (every lane moves the sample pairs it wrote itself)
     const float* line = glw_signal_line<kNR>(smem, wv);

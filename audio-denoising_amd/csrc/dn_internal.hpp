@@ -241,7 +241,8 @@ void launch_sess_export(const SessArgs& a, const SessRec& r, int n_fft, void* re
 constexpr uint32_t kSessRecBadMagic = 1, kSessRecBadVersion = 2, kSessRecBadGeometry = 3, kSessRecBadPushes = 4;
 void launch_sess_check(const SessArgs& a, const SessRec& r, const void* records, uint32_t* status, hipStream_t st);
 void launch_sess_import(const SessArgs& a, const SessRec& r, int n_fft, const void* records, const uint64_t* sids_in, hipStream_t st);
-// N consecutive hops of B streams in one call (dn_clip.hip; dn_clip_process).  Frame f = b N + i is hop i of stream b.
+// N consecutive hops of B streams in one call (dn_clip.hip; dn_clip_process).  Frame f = b N + i is hop i of stream b.  Ragged
+// (dn_clip_process_ragged): stream b runs off[b + 1] - off[b] hops, frame f = off[b] + i.
 constexpr long kClipGlwAutoFrames = 1024;       // n_fft 1024: from this many frames (B x N) on a call runs its chains a wavefront per frame (measured, profiles/clip_time.txt: per column / per frame 0.87 at 256 frames, 1.03 at 1,024, 1.15 at 4,096, 1.28 at 24,000)
 constexpr int kClipRow1024 = 1540;               // floats of a frame row at n_fft 1024: the linear magnitudes [3][513], in whole 16-byte units (else n_fft: the samples)
 struct ClipArgs {
@@ -256,6 +257,9 @@ struct ClipArgs {
     float* mel; float* diff; float* peak;                       //            [B N][3][M], [B N][3][M], [B N]
     int per_stream;                                             // chains a wavefront per frame (n_fft 1024) instead of a wavefront per column
     float* phas;                                                // DN_PHASE_FROM_INPUT: workspace rows [B N][3][K] complex, written by the analysis, the chains' init; else null
+    // ragged call (dn_clip_process_ragged), else both null: stream b owns frames off[b] .. off[b + 1] (off[0] = 0, off[B] = frames; N unused), its
+    // rows of hops_in / hops_out start at off[b] hop, and its hop i draws from (seed + frame0[b] + i, sid0 + b)
+    const int* off; const uint64_t* frame0;                     // [B + 1], [B], at the head of the workspace
 };
 void launch_clip(const DspDev& d, const CellDev* c_dev, const ClipArgs& a, bool bf16, hipStream_t st);
 void launch_cell_bf16(const CellDev& c, const float* x, const float* hx_in, float* out, float* hx_out, int B, int T,

@@ -209,6 +209,132 @@ class Denoiser:
         out = self._clip(padded[:, self.hop:].contiguous(), ring, ola, self.init_hx(B), init_angles, seed, stream_id0, frame_cap)
         return out[:, self.hop:self.hop + L].contiguous()
 
+    # -- clip mode, ragged: every stream its own number of hops
+    def _clip_ragged_call(self, tin, n, f0, ring, ola, hx, tout, ia, seed, stream_id0, gl):
+        """one dn_clip_process_ragged call: stream b runs ``n[b]`` hops of the packed ``tin`` from hop ``f0[b]`` of its seed sequence on"""
+        B, F = len(n), sum(n)
+        need = self.lib.dn_clip_ragged_workspace_bytes(self.plan.handle, B, F, self._flags())
+        if self._clip_ws is None or self._clip_ws.numel() < need:
+            self._clip_ws = torch.empty(need, dtype=torch.uint8, device=self.device)
+        s16 = tin.dtype == torch.int16
+        model_h = self.model._native(self.device)
+        with torch.cuda.device(self.device):
+            st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+            self.lib.check(self.lib.dn_clip_process_ragged(model_h, self.plan.handle, tin.data_ptr(), int(s16), ring.data_ptr(), ola.data_ptr(), hx.data_ptr(),
+                                                           tout.data_ptr(), int(s16), None if ia is None else ia.data_ptr(), seed, stream_id0,
+                                                           (C.c_int32 * B)(*n), (C.c_uint64 * B)(*[v & (2 ** 64 - 1) for v in f0]), self.n_iter,
+                                                           self.momentum, self._clip_ws.data_ptr(), B, self._flags() | gl, st))
+
+    def clip_ragged(self, hops_in: torch.Tensor, n_hops, ring: torch.Tensor, ola: torch.Tensor, hx: torch.Tensor, frame0=None, seed: int = 0,
+                    stream_id0: int = 0, init_angles: torch.Tensor | None = None, frame_cap: int | None = None, gl: int = 0) -> torch.Tensor:
+        """Clips of different lengths in one call (dn_clip_process_ragged): stream b runs ``n_hops[b]`` hops (0: the stream is left as it is) of the
+        packed ``hops_in`` (F * hop,) float32 or int16 on the device, F = sum n_hops, stream b's hops behind those of the streams before it.  Exactly
+        ``n_hops[b]`` ``dn_stream_step`` calls on row b of ``ring``, ``ola`` (B, n_fft) and ``hx`` (B, 17, C), advanced in place; hop i of stream b
+        draws from ``(seed + frame0[b] + i, stream_id0 + b)`` (``frame0``: B ints, default zeros) or takes ``init_angles[off[b] + i]`` of the
+        packed (F, K, 3) complex64.  Returns the packed hops out, in the dtype of ``hops_in``.  At most ``frame_cap`` frames go into one call
+        (default ``CLIP_FRAME_CAP``): in rounds, every stream with hops left runs an equal share of the cap (at most what it has left; streams
+        beyond the cap wait with 0 hops), its ``frame0`` moved on by what it has run."""
+        n_hops = [int(v) for v in n_hops]
+        B, F = len(n_hops), sum(n_hops)
+        frame0 = [0] * B if frame0 is None else [int(v) for v in frame0]
+        cap = self.CLIP_FRAME_CAP if frame_cap is None else int(frame_cap)
+        if cap < 1:
+            raise ValueError("the frame cap must be positive")
+        if B < 1 or len(frame0) != B or min(n_hops) < 0:
+            raise ValueError("n_hops: one entry >= 0 per stream, at least one stream; frame0: one entry per stream")
+        if hops_in.dim() != 1 or hops_in.dtype not in (torch.float32, torch.int16) or hops_in.numel() != F * self.hop or not hops_in.is_contiguous():
+            raise ValueError(f"hops_in must be contiguous float32 or int16 of shape ({F * self.hop},): sum(n_hops) hops, packed")
+        if hops_in.device != self.device:
+            raise RuntimeError(f"hops_in must live on {self.device} (no CPU path)")
+        self._check(ring, (B, self.n_fft), "ring")
+        self._check(ola, (B, self.n_fft), "ola")
+        self._check(hx, (B, self.model.latent_size, self.num_compressed_bins), "hx")
+        ia = None
+        if init_angles is not None:
+            if self.phase == "input":
+                raise ValueError("this denoiser takes its initial phases from the input (phase='input'): init_angles cannot be passed")
+            if tuple(init_angles.shape) != (F, self.n_stft, 3) or init_angles.dtype != torch.complex64:
+                raise ValueError(f"init_angles must be complex64 of shape {(F, self.n_stft, 3)}")
+            ia = torch.view_as_real(init_angles.to(self.device).transpose(-1, -2).contiguous())          # [F][3][K] interleaved
+        out = torch.empty_like(hops_in)
+        if F == 0:
+            return out
+        if F <= cap:
+            self._clip_ragged_call(hops_in, n_hops, frame0, ring, ola, hx, out, ia, seed, stream_id0, gl)
+            return out
+        off = [0] * (B + 1)
+        for b in range(B):
+            off[b + 1] = off[b] + n_hops[b]
+        done = [0] * B
+        while True:
+            live = [b for b in range(B) if done[b] < n_hops[b]][:cap]
+            if not live:
+                return out
+            q = cap // len(live)
+            n = [0] * B
+            for b in live:
+                n[b] = min(n_hops[b] - done[b], q)
+            rows = torch.cat([torch.arange(off[b] + done[b], off[b] + done[b] + n[b]) for b in live]).to(self.device)          # the round's frames
+            tin = hops_in.view(F, self.hop)[rows].reshape(-1)
+            tout = torch.empty_like(tin)
+            self._clip_ragged_call(tin, n, [frame0[b] + done[b] for b in range(B)], ring, ola, hx, tout, None if ia is None else ia[rows].contiguous(),
+                                   seed, stream_id0, gl)
+            out.view(F, self.hop)[rows] = tout.view(-1, self.hop)
+            for b in live:
+                done[b] += n[b]
+
+    def denoise_clips(self, waves, seed: int = 0, stream_id0: int = 0, init_angles=None, frame_cap: int | None = None):
+        """Offline, clips of any lengths: ``waves`` is a list of 1-D float32 or int16 tensors on the device; returns the list of denoised clips, same
+        lengths and dtypes (an empty tensor for an empty one).  Element b is ``denoise_clip(waves[b][None], seed, stream_id0 + b)[0]`` bit for bit --
+        the priming hop, the zero-padding to ``clip_hops(L_b)`` hops, the dropped first hop, the int16 convention -- with every clip's frames in one
+        ``dn_clip_process_ragged`` call per dtype (``clip_ragged``).  ``init_angles``: per clip a sequence of ``clip_hops(L_b)`` tensors (K, 3)
+        complex64 (none for an empty clip)."""
+        waves = list(waves)
+        B = len(waves)
+        for w in waves:
+            if w.dim() != 1 or w.device != self.device or w.dtype not in (torch.float32, torch.int16):
+                raise ValueError(f"waves must be 1-D float32 or int16 tensors on {self.device}")
+        if init_angles is not None:
+            if self.phase == "input":
+                raise ValueError("this denoiser takes its initial phases from the input (phase='input'): init_angles cannot be passed")
+            if len(init_angles) != B:
+                raise ValueError("init_angles: one sequence of phases per clip")
+        n_hops = [self.clip_hops(w.numel()) if w.numel() else 0 for w in waves]
+        outs = [torch.empty_like(w) for w in waves]
+        if B == 0 or sum(n_hops) == 0:
+            return outs
+        ring = torch.zeros(B, self.n_fft, dtype=torch.float32, device=self.device)
+        ola, hx = torch.zeros_like(ring), self.init_hx(B)
+        for dtype in (torch.float32, torch.int16):          # the packed hops of a call have one sample format: the other format's clips wait with 0 hops
+            n = [n_hops[b] if waves[b].dtype == dtype else 0 for b in range(B)]
+            F = sum(n)
+            if F == 0:
+                continue
+            packed = torch.zeros(F * self.hop, dtype=dtype, device=self.device)
+            ia, at = [], 0
+            for b in range(B):
+                if n[b] == 0:
+                    continue
+                w, L = waves[b], waves[b].numel()
+                head = min(L, self.hop)          # the priming hop goes into the ring, the rest is the stream's hops, zero-padded
+                first = torch.zeros(self.hop, dtype=dtype, device=self.device)
+                first[:head] = w[:head]
+                # (int16 -> float32 as the kernels do it: a true division, by a tensor -- a Python scalar would become a multiplication by its reciprocal)
+                ring[b, self.hop:] = first.float() / torch.tensor(32767.0, device=self.device) if dtype == torch.int16 else first
+                packed[at * self.hop:at * self.hop + L - head] = w[head:]
+                if init_angles is not None:
+                    if len(init_angles[b]) != n[b]:
+                        raise ValueError(f"init_angles[{b}]: one set of phases for each of the {n[b]} hops")
+                    ia += [z.to(self.device) for z in init_angles[b]]
+                at += n[b]
+            out = self.clip_ragged(packed, n, ring, ola, hx, None, seed, stream_id0, torch.stack(ia) if ia else None, frame_cap)
+            at = 0
+            for b in range(B):
+                if n[b]:
+                    outs[b] = out[(at + 1) * self.hop:(at + 1) * self.hop + waves[b].numel()].clone()
+                    at += n[b]
+        return outs
+
     def process_frame_(self, frames: torch.Tensor, hx: torch.Tensor, out: torch.Tensor, seed: int = 0, stream_id0: int = 0) -> None:
         """Allocation-free variant for steady-state loops and hipGraph capture: ``hx`` is advanced in place and
         the denoised frames are written to ``out``; initial phases come from the device generator."""

@@ -28,6 +28,7 @@
  *   dn_process_frame                    app3.py:178-217  the whole per-hop loop body for B streams
  *   dn_stream_step                      app3.py:178-226  the same plus ring buffer / overlap-add state (P12)
  *   dn_clip_process                     app3.py:178-226  N consecutive dn_stream_step calls in one: audio that is already there
+ *   dn_clip_process_ragged              app3.py:178-226  the same for clips of different lengths: n_hops[b] hops of stream b
  *   dn_sessions_*                       app3.py:123-250  one DenoisingAudioProcessor per session: slots that join, leave
  *                                       and push hops on their own, batched per tick; sessions exported to and
  *                                       imported from self-contained records (move, resume, resize a pool)
@@ -314,6 +315,35 @@ int dn_clip_process(const dn_model* m, const dn_dsp* d, const void* hops_in, int
                     float* hx, void* hops_out, int32_t out_s16, const float* init_angles, uint64_t seed,
                     uint64_t stream_id0, int32_t n_iter, float momentum, void* workspace, int32_t B, int32_t N,
                     uint32_t flags, void* stream);
+
+/* ---- Clip mode, ragged: every stream its own number of hops ---------------------------------------------
+ * Clips of different lengths (a folder of files, a batch of uploads, a backlog) in ONE call.  For every stream b with
+ * n_hops[b] >= 1 the call does exactly what dn_clip_process does with B = 1, N = n_hops[b], seed + frame0[b] and
+ * stream_id0 + b on that stream's rows -- n_hops[b] consecutive dn_stream_step calls, the same hops out, ring, ola and hx,
+ * bit for bit: hop i of stream b draws from (seed + frame0[b] + i, stream_id0 + b).  With F = sum n_hops and
+ * off[b] = n_hops[0] + ... + n_hops[b-1]:
+ *   n_hops  [host][B]  >= 0;   frame0 [host][B] or NULL (zeros).  Both are the caller's again when the call returns.
+ *   hops_in, hops_out [dev][F*hop]  packed, float32 or int16 as in the uniform call: stream b's hops start at off[b]*hop
+ *   init_angles [dev][F][3][K] complex or NULL, frame off[b] + i = hop i of stream b
+ *   ring, ola [dev][B][n_fft], hx [dev][B][17][C] as in the uniform call.  A stream with n_hops[b] == 0 has no rows in the
+ *   packed arrays and is left exactly as it was: no byte of its ring, ola or hx is written.
+ *   workspace [dev] of dn_clip_ragged_workspace_bytes(d, B, F, flags) bytes, 16-byte aligned: the table -- off [B+1] int32,
+ *   padded to an 8-byte boundary, then frame0 [B] uint64 -- rounded up to 256 bytes, then the uniform call's layout for F
+ *   frames (frame rows | mel | residual | peak, rounded up to 256 bytes, plus 256; the phasor rows with
+ *   DN_PHASE_FROM_INPUT).  The size depends on B only through the table; it is 0 for a null plan, B < 1, total_hops < 1,
+ *   total_hops > 2^22 or unknown flag bits.
+ * flags and their refusals are the uniform call's (with neither chain flag n_fft 1024 runs a wavefront per frame from 1,024
+ * frames F on).  Everything is validated on the host before anything is enqueued -- B >= 1, n_hops non-NULL and every entry
+ * >= 0, F <= 2^22, non-NULL pointers when F > 0 -- so a failed call leaves ring, ola, hx, hops_out and the workspace
+ * untouched; F == 0 returns DN_OK with nothing enqueued.  A frame finds its stream by bisection in off on the device.
+ * The library builds the table in host memory of its own and copies it to the head of the workspace with a stream-ordered
+ * copy on `stream`.  That source is pageable, so the copy completes before the call returns: this is the one clip call
+ * that may wait for earlier work on `stream`, and it cannot be captured into a hipGraph. */
+size_t dn_clip_ragged_workspace_bytes(const dn_dsp* d, int32_t B, int64_t total_hops, uint32_t flags);
+int dn_clip_process_ragged(const dn_model* m, const dn_dsp* d, const void* hops_in, int32_t in_s16, float* ring, float* ola,
+                           float* hx, void* hops_out, int32_t out_s16, const float* init_angles, uint64_t seed,
+                           uint64_t stream_id0, const int32_t* n_hops, const uint64_t* frame0, int32_t n_iter,
+                           float momentum, void* workspace, int32_t B, uint32_t flags, void* stream);
 
 /* ---- Software-pipelined hops ------------------------------------------------------------------------
  * Consecutive hops depend on each other only through hx (the model); hop n's Griffin-Lim (~3/4 of a hop) is
