@@ -33,6 +33,8 @@ SYMBOLS = (
     "dn_stft_phasors", "dn_workspace_bytes_ex", "dn_clip_workspace_bytes_ex",
     "dn_griffinlim_general_whole_max", "dn_griffinlim_general_workspace_bytes", "dn_griffinlim_general", "dn_griffinlim_draw_phases_general",
     "dn_server_mag",
+    "dn_resample_create", "dn_resample_destroy", "dn_resample_geometry", "dn_resample_get_kernel", "dn_resample_out_len", "dn_resample",
+    "dn_resample_state_bytes", "dn_resample_push",
 )
 
 DN_PEAK_NORMALIZE = 1
@@ -62,6 +64,10 @@ class MomoCfg(C.Structure):
 
 class DspCfg(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("sample_rate", "n_fft", "hop", "n_mels")]
+
+
+class ResampleCfg(C.Structure):
+    _fields_ = [("orig_freq", C.c_int32), ("new_freq", C.c_int32), ("lowpass_filter_width", C.c_int32), ("rolloff", C.c_double)]
 
 
 class DnError(RuntimeError):
@@ -168,6 +174,17 @@ class DnLib:
         L.dn_griffinlim_general.argtypes = [vp, p, p, u64, u64, p, vp, i32, i32, i32, f32, u32, vp]
         L.dn_griffinlim_draw_phases_general.argtypes = [vp, u64, u64, p, i32, i32, vp]
         L.dn_server_mag.argtypes = [vp, p, p, p, i32, vp]
+        L.dn_resample_create.argtypes = [C.POINTER(ResampleCfg), vp, C.POINTER(vp)]
+        L.dn_resample_destroy.argtypes = [vp]
+        L.dn_resample_destroy.restype = None
+        L.dn_resample_geometry.argtypes = [vp] + [C.POINTER(i32)] * 5
+        L.dn_resample_get_kernel.argtypes = [vp, vp]
+        L.dn_resample_out_len.argtypes = [vp, i64]
+        L.dn_resample_out_len.restype = i64
+        L.dn_resample.argtypes = [vp, p, i32, p, i32, i32, i64, i64, i64, vp]
+        L.dn_resample_state_bytes.argtypes = [vp, i32]
+        L.dn_resample_state_bytes.restype = C.c_size_t
+        L.dn_resample_push.argtypes = [vp, p, p, i32, p, i32, i32, i64, i64, i64, vp]
         if L.dn_abi_version() != ABI_VERSION:
             raise ImportError(f"{path}: ABI version {L.dn_abi_version()} != {ABI_VERSION}; rebuild the extension")
 

@@ -234,6 +234,16 @@ struct dn_sessions {
     uint32_t* chk_dev = nullptr;
 };
 
+struct dn_resampler {
+    dn_resample_cfg cfg;
+    int o = 0, n = 0, width = 0, KW = 0, D = 0, H = 0;     // reduced rates; taps 2 width + o; delay blocks ceil(width / o); history D o + width
+    bool small = false;                       // the block-per-lane kernel (dn_resample.hip), else the phase-per-lane one
+    int np = 0;                               // general form: phases of a device table row (n rounded up to even)
+    std::vector<float> kernel;                // host copy [n][KW], what dn_resample_get_kernel returns
+    DevArena arena;                           // the table as the handle's kernel form reads it
+    const float* table = nullptr;
+};
+
 // ------------------------------------------------------------------ shared between the units
 constexpr uint32_t kHopFlags = DN_CONV_BF16 | DN_PHASE_FROM_INPUT;      // the flag bits of a hop, a pipe and a pool
 

@@ -284,6 +284,28 @@ struct GlgArgs {
 void launch_glg_whole(const DspDev& d, const GlgArgs& a, hipStream_t st);
 void launch_glg_steps(const DspDev& d, const GlgArgs& a, hipStream_t st);
 void launch_draw_phases_general(const DspDev& d, float* out, uint64_t seed, uint64_t sid0, int B, int T, hipStream_t st);
+// Polyphase sinc resampling (dn_resample.hip; dn_resample, dn_resample_push).  A row's virtual input v is `lead` samples -- hist [B][lead], or
+// zeros when hist is null -- followed by the Lx samples of x and zeros beyond; output q n + p of the row (below Ly) is ONE chain
+// acc = fmaf(k[p][j], v[q o + j], acc), j ascending from acc = 0, in both kernel forms.  The whole-signal call has lead = width and no hist, a
+// push lead = H and hist = the stream's state: the same body, the same bits.
+constexpr int kRsSmallMaxN = 4, kRsSmallMaxO = 8, kRsSmallMaxTable = 512;       // the block-per-lane form: n <= 4, o <= 8, n KW <= 512 floats (table in LDS)
+constexpr int kRsThreads = 256, kRsTileQ = 512;                                                    // small form: blocks a workgroup, two a lane
+constexpr int kRsGenThreads = 128, kRsGenPhases = 2 * kRsGenThreads, kRsGenBlocks = 4;      // general form: phases and blocks a workgroup
+constexpr int kRsMaxLen = 1 << 30;                                               // samples of a row, in and out: every 32-bit index stays in range
+struct ResampleArgs {
+    const void* x; int in_s16; long long x_stride; int Lx;      // [B][x_stride] float32 or int16 (x / 32767)
+    const float* hist; int lead;                                 // [B][lead] or null
+    void* y; int out_s16; long long y_stride; int Ly;            // [B][y_stride] float32 or int16 (clip, * 32767, truncate)
+    const float* table;                                          // small form: [n][KW]; general form: tap-major [KW][np], np = n rounded up to even
+    int o, n, KW, np;
+    int B, nblk;                                                 // rows; blocks of n outputs a row: ceil(Ly / n)
+    int small;                                                   // which form the handle was built for
+    int x_vec, y_pair;                                           // x rows start on 4-element boundaries; y rows start on 2-element boundaries
+};
+void launch_resample(const ResampleArgs& a, hipStream_t st);
+// state [B][H] <- the last H samples of [state | chunk], chunk [B][x_stride] with Lc >= 1 samples a row: one workgroup per stream, after the
+// launch that read the old state (stream order)
+void launch_resample_state(float* state, int H, const void* x, int in_s16, long long x_stride, int Lc, int B, hipStream_t st);
 
 }  // namespace dn
 

@@ -17,7 +17,7 @@ import torch
 
 from . import _lib
 from .gruunet2 import GRUUNet2
-from .transforms import DspPlan, melscale_fbanks
+from .transforms import DspPlan, Resample, melscale_fbanks
 
 
 class Denoiser:
@@ -49,6 +49,7 @@ class Denoiser:
         self.plan = DspPlan(self.device, sample_rate, n_fft, hop_length, n_mels, fb=fb, window=torch.hann_window(n_fft) if window is None else window)
         self._ws = None
         self._clip_ws = None
+        self._resamplers = {}
         self._calls = 0
 
     def _flags(self) -> int:
@@ -185,17 +186,37 @@ class Denoiser:
                     out[:, n0 * self.hop:(n0 + n) * self.hop] = tout
         return out
 
-    def denoise_clip(self, wave: torch.Tensor, seed: int = 0, stream_id0: int = 0, init_angles=None, frame_cap: int | None = None) -> torch.Tensor:
+    def resamplers(self, sample_rate: int):
+        """(``Resample(sample_rate, plan rate)``, ``Resample(plan rate, sample_rate)``): the pair the offline front ends wrap around the hop path
+        for audio at another rate (built once per rate)."""
+        rate = int(sample_rate)
+        if rate != sample_rate or rate < 1:
+            raise ValueError("sample_rate must be a positive integer")
+        pair = self._resamplers.get(rate)
+        if pair is None:
+            pair = self._resamplers[rate] = (Resample(rate, self.sample_rate), Resample(self.sample_rate, rate))
+        return pair
+
+    def denoise_clip(self, wave: torch.Tensor, seed: int = 0, stream_id0: int = 0, init_angles=None, frame_cap: int | None = None,
+                     sample_rate: int | None = None) -> torch.Tensor:
         """Offline: ``wave`` (B, L) float32 or int16 PCM on the device -> the denoised clips, same shape and dtype, output sample n lined up with
         input sample n.  What a fresh ``DenoiserStream`` emits for the clip -- the first hop primes the ring, the clip is zero-padded to whole
         hops plus the two that drain the overlap-add line, the first emitted hop (the zeros of the empty line) is dropped -- computed by
         ``dn_clip_process``: all frames analysed at once, the model hop by hop, every Griffin-Lim chain side by side.  Hop i of stream b draws
-        its phases from ``(seed + i, stream_id0 + b)``, or takes ``init_angles[i]`` (B, K, 3) complex64, ``clip_hops(L)`` of them."""
+        its phases from ``(seed + i, stream_id0 + b)``, or takes ``init_angles[i]`` (B, K, 3) complex64, ``clip_hops(L)`` of them.
+
+        ``sample_rate``: the rate of ``wave`` when it is not the plan's (utils.py:48-49 wraps the model in the same pair of transforms).  The clips
+        are resampled to the plan's rate on the device (``transforms.Resample``), denoised by exactly the path above, resampled back and trimmed
+        to L samples -- bit for bit that composition, in the dtype of the input; the filters are symmetric, so output sample n still lines up
+        with input sample n.  ``init_angles`` then counts the hops of the resampled clip.  ``None`` (or the plan's rate): exactly the call above."""
         if wave.dim() != 2 or wave.device != self.device or wave.dtype not in (torch.float32, torch.int16):
             raise ValueError(f"wave must be float32 or int16 (B, L) on {self.device}")
         B, L = wave.shape
         if B == 0 or L == 0:
             return torch.empty_like(wave)
+        if sample_rate is not None and int(sample_rate) != self.sample_rate:
+            rin, rout = self.resamplers(sample_rate)
+            return rout(self.denoise_clip(rin(wave), seed, stream_id0, init_angles, frame_cap))[:, :L].contiguous()
         n_hops = self.clip_hops(L)
         if init_angles is not None and len(init_angles) != n_hops:
             raise ValueError(f"init_angles: one set of phases for each of the {n_hops} hops")
@@ -283,17 +304,52 @@ class Denoiser:
             for b in live:
                 done[b] += n[b]
 
-    def denoise_clips(self, waves, seed: int = 0, stream_id0: int = 0, init_angles=None, frame_cap: int | None = None):
+    def _resample_group(self, waves, resample: Resample):
+        """1-D clips of one dtype through ``resample`` in ONE call, as zero-padded rows: the zeros behind a row add k * 0 terms to the row's own
+        outputs and nothing else, so element i is ``resample(waves[i])`` bit for bit"""
+        lens = [w.numel() for w in waves]
+        rows = torch.zeros(len(waves), max(lens), dtype=waves[0].dtype, device=self.device)
+        for i, w in enumerate(waves):
+            rows[i, :lens[i]] = w
+        out = resample(rows)
+        return [out[i, :resample.out_len(lens[i])].clone() for i in range(len(waves))]
+
+    def _resample_clips(self, waves, rates, to_plan: bool, lengths=None):
+        """every clip whose rate differs from the plan's, grouped by (rate, dtype), through its group's resampler (towards the plan's rate, or back
+        and trimmed to ``lengths``); the others as they are"""
+        out = list(waves)
+        groups = {}
+        for b, w in enumerate(waves):
+            if rates[b] != self.sample_rate and w.numel():
+                groups.setdefault((rates[b], w.dtype), []).append(b)
+        for (rate, _), idx in groups.items():
+            res = self._resample_group([waves[b] for b in idx], self.resamplers(rate)[0 if to_plan else 1])
+            for b, y in zip(idx, res):
+                out[b] = y if lengths is None else y[:lengths[b]].clone()
+        return out
+
+    def denoise_clips(self, waves, seed: int = 0, stream_id0: int = 0, init_angles=None, frame_cap: int | None = None, sample_rates=None):
         """Offline, clips of any lengths: ``waves`` is a list of 1-D float32 or int16 tensors on the device; returns the list of denoised clips, same
         lengths and dtypes (an empty tensor for an empty one).  Element b is ``denoise_clip(waves[b][None], seed, stream_id0 + b)[0]`` bit for bit --
         the priming hop, the zero-padding to ``clip_hops(L_b)`` hops, the dropped first hop, the int16 convention -- with every clip's frames in one
         ``dn_clip_process_ragged`` call per dtype (``clip_ragged``).  ``init_angles``: per clip a sequence of ``clip_hops(L_b)`` tensors (K, 3)
-        complex64 (none for an empty clip)."""
+        complex64 (none for an empty clip).
+
+        ``sample_rates``: an int, or one per clip -- the rates the clips arrive at.  Clips at another rate than the plan's are resampled to it
+        and back as ``denoise_clip(.., sample_rate=r)`` does, bit for bit, one resampler call per (rate, dtype) group on zero-padded rows each way.
+        ``None``: exactly the call above."""
         waves = list(waves)
         B = len(waves)
         for w in waves:
             if w.dim() != 1 or w.device != self.device or w.dtype not in (torch.float32, torch.int16):
                 raise ValueError(f"waves must be 1-D float32 or int16 tensors on {self.device}")
+        if sample_rates is not None:
+            rates = [int(r) for r in sample_rates] if hasattr(sample_rates, "__len__") else [int(sample_rates)] * B
+            if len(rates) != B:
+                raise ValueError("sample_rates: an int, or one rate per clip")
+            if any(r != self.sample_rate for r in rates):
+                at_plan = self._resample_clips(waves, rates, True)
+                return self._resample_clips(self.denoise_clips(at_plan, seed, stream_id0, init_angles, frame_cap), rates, False, [w.numel() for w in waves])
         if init_angles is not None:
             if self.phase == "input":
                 raise ValueError("this denoiser takes its initial phases from the input (phase='input'): init_angles cannot be passed")

@@ -6,6 +6,7 @@
     InverseMelScale(n_mels, n_stft, sample_rate)                              app3.py:145-148
     GriffinLim(n_fft, win_length, hop_length, window_fn, power=1.0)           app3.py:149-153
     InverseSpectrogram(n_fft, win_length, hop_length)                         server.py:174
+    Resample(orig_freq, new_freq)                                             utils.py:48-49 (app.py:181: librosa.resample)
 
 Each ``forward`` is one HIP kernel launch through the C ABI; inputs must be float32 (complex64 for
 InverseSpectrogram) CUDA tensors shaped as the reference shapes them.  Internally every spectral
@@ -348,3 +349,187 @@ class InverseSpectrogram(_PlanModule):
             else:
                 plan.lib.check(plan.lib.dn_istft_general(plan.handle, rows.data_ptr(), wave.data_ptr(), B, T, _stream_ptr(rows.device)))
         return wave
+
+
+class Resample(nn.Module):
+    """Resample(orig_freq, new_freq, resampling_method, lowpass_filter_width, rolloff, beta, *, dtype): (.., L) -> (.., ceil(new L / orig)) with
+    the rates reduced by their gcd, float32 or int16 PCM on the device, the dtype of the input (dn_resample: one launch, polyphase sinc filter).
+    utils.py:48-49 (``Resample(44100, SR)``, ``Resample(SR, 44100)``), app.py:181 (``librosa.resample``).
+
+    ``sinc_interp_hann`` is the table the library builds itself in double; ``sinc_interp_kaiser`` (``beta`` default 14.769656459379492) is built
+    here with ``torch.i0`` in float64 and handed in.  Either way the table is rounded to float32 once; ``dtype`` (torchaudio's precision of the
+    precomputed kernel) is accepted and changes nothing.  int16 is read as x / 32767 and written clip, * 32767, truncate, as everywhere in this
+    package.  Rows that are contiguous in themselves go through their stride (a slice of a wider batch is not copied).  Equal rates return the input
+    itself, as torchaudio does.  No CPU path."""
+
+    def __init__(self, orig_freq: int = 16000, new_freq: int = 16000, resampling_method: str = "sinc_interp_hann", lowpass_filter_width: int = 6,
+                 rolloff: float = 0.99, beta: float | None = None, *, dtype: torch.dtype | None = None):
+        super().__init__()
+        if resampling_method not in ("sinc_interp_hann", "sinc_interp_kaiser"):
+            raise ValueError(f"Invalid resampling method: {resampling_method}")
+        if int(orig_freq) != orig_freq or int(new_freq) != new_freq:
+            raise ValueError("Frequencies must be of integer type to ensure quality resampling computation.")
+        if dtype is not None and not dtype.is_floating_point:
+            raise TypeError(f"dtype must be a floating point type, got {dtype}")
+        self.orig_freq, self.new_freq = int(orig_freq), int(new_freq)
+        self.resampling_method, self.lowpass_filter_width, self.rolloff, self.beta = resampling_method, int(lowpass_filter_width), float(rolloff), beta
+        if self.orig_freq < 1 or self.new_freq < 1 or self.lowpass_filter_width < 1 or not 0.0 < self.rolloff <= 1.0:
+            raise ValueError("rates must be positive, lowpass_filter_width at least 1 and rolloff in (0, 1]")
+        # the geometry, as torchaudio's _get_sinc_resample_kernel has it (the library computes the same and is asked when a handle is built)
+        g = math.gcd(self.orig_freq, self.new_freq)
+        self.o, self.n = self.orig_freq // g, self.new_freq // g
+        self.width = math.ceil(self.lowpass_filter_width * self.o / (min(self.o, self.n) * self.rolloff))
+        self.taps = 2 * self.width + self.o
+        self.delay_blocks = -(-self.width // self.o)
+        if self.orig_freq != self.new_freq and (max(self.o, self.n) > 1024 or self.n * self.taps > 2 ** 19):
+            raise NotImplementedError(f"the kernels take reduced rates up to 1024 and tables of up to 2^19 floats; {self.orig_freq} -> {self.new_freq} is "
+                                      f"{self.o} : {self.n} with {self.n} x {self.taps} floats")
+        self._handles = {}
+
+    @property
+    def lib(self):
+        """the product's library, loaded on first use (constructing the transform needs neither the library nor a device)"""
+        return _lib.get_lib()
+
+    def _create(self, table):
+        h = C.c_void_p()
+        cfg = _lib.ResampleCfg(self.orig_freq, self.new_freq, self.lowpass_filter_width, self.rolloff)
+        self.lib.check(self.lib.dn_resample_create(C.byref(cfg), None if table is None else C.c_void_p(table.data_ptr()), C.byref(h)))
+        v = [C.c_int32() for _ in range(5)]
+        self.lib.check(self.lib.dn_resample_geometry(h, *[C.byref(x) for x in v]))
+        if tuple(x.value for x in v) != (self.o, self.n, self.width, self.taps, self.delay_blocks):
+            self.lib.dn_resample_destroy(h)
+            raise RuntimeError("the library's resampler geometry differs from this module's")
+        return h
+
+    def _kaiser_table(self) -> torch.Tensor:
+        """torchaudio's sinc_interp_kaiser kernel, (n, taps), in float64, rounded once"""
+        beta = 14.769656459379492 if self.beta is None else float(self.beta)
+        o, n, lpw = self.o, self.n, self.lowpass_filter_width
+        base = min(o, n) * self.rolloff
+        idx = torch.arange(-self.width, self.width + o, dtype=torch.float64)[None, :] / o
+        t = (torch.arange(0, -n, -1, dtype=torch.float64)[:, None] / n + idx) * base
+        t = t.clamp(-lpw, lpw)
+        window = torch.i0(beta * torch.sqrt(1 - (t / lpw) ** 2)) / torch.i0(torch.tensor(beta, dtype=torch.float64))
+        t = t * math.pi
+        sinc = torch.where(t == 0, torch.ones_like(t), t.sin() / t)
+        return (sinc * (window * (base / o))).to(torch.float32).contiguous()
+
+    def handle(self, device: torch.device):
+        """the dn_resampler of ``device`` (built on first use)"""
+        idx = device.index if device.index is not None else torch.cuda.current_device()
+        h = self._handles.get(idx)
+        if h is None:
+            table = self._kaiser_table() if self.resampling_method == "sinc_interp_kaiser" else None
+            with torch.cuda.device(idx):
+                h = self._create(table)
+            self._handles[idx] = h
+            weakref.finalize(self, self.lib.dn_resample_destroy, h)
+        return h
+
+    def kernel(self, device: torch.device) -> torch.Tensor:
+        """the float32 table (n, taps) as the library holds it"""
+        k = torch.empty(self.n, self.taps)
+        self.lib.check(self.lib.dn_resample_get_kernel(self.handle(torch.device(device)), k.data_ptr()))
+        return k
+
+    def out_len(self, length: int) -> int:
+        return -(-self.n * int(length) // self.o)
+
+    def __deepcopy__(self, memo):
+        new = self.__class__.__new__(self.__class__)
+        memo[id(self)] = new
+        import copy
+        for k, v in self.__dict__.items():
+            new.__dict__[k] = {} if k == "_handles" else copy.deepcopy(v, memo)
+        return new
+
+    @staticmethod
+    def _rows(t: torch.Tensor):
+        """(.., L) -> (a 2-D tensor whose rows are contiguous in themselves, its row stride): a view wherever the strides allow it"""
+        L = t.shape[-1]
+        if t.dim() == 1:
+            t = t.unsqueeze(0)
+        if t.dim() > 2:
+            t = t.reshape(-1, L)          # (a view when the leading dimensions fold, else a copy)
+        if L > 1 and t.stride(1) != 1:
+            t = t.contiguous()
+        stride = t.stride(0) if t.shape[0] > 1 else L
+        if stride < L:                    # expanded or overlapping rows
+            t = t.contiguous()
+            stride = L
+        return t, stride
+
+    def forward(self, waveform: torch.Tensor) -> torch.Tensor:
+        if not waveform.is_cuda:
+            raise RuntimeError("Resample: expected a CUDA tensor (this package has no CPU path)")
+        if waveform.dtype not in (torch.float32, torch.int16):
+            raise TypeError(f"Resample: expected torch.float32 or torch.int16, got {waveform.dtype}")
+        if self.orig_freq == self.new_freq:
+            return waveform
+        L = waveform.shape[-1]
+        lead = waveform.shape[:-1]
+        Ly = self.out_len(L)
+        out = torch.empty(lead + (Ly,), dtype=waveform.dtype, device=waveform.device)
+        if L == 0 or out.numel() == 0:
+            return out
+        x, xs = self._rows(waveform)
+        s16 = int(waveform.dtype == torch.int16)
+        with torch.cuda.device(waveform.device):
+            self.lib.check(self.lib.dn_resample(self.handle(waveform.device), x.data_ptr(), s16, out.data_ptr(), s16, x.shape[0], L, xs, Ly,
+                                                _stream_ptr(waveform.device)))
+        return out
+
+
+class ResampleStream:
+    """``batch`` live streams through one ``Resample`` (dn_resample_push).  ``push(chunk)`` takes (batch, k o) samples, whole blocks of
+    ``resample.o``, float32 or int16 on the device, and returns the (batch, k n) samples they emit (k = 0: an empty tensor, nothing changes).
+    The outputs lag the input by ``delay`` output samples (D n, D = ceil(width / o) blocks): the concatenation of everything pushed and then ``flush()`` -- D blocks of zeros --, from sample
+    ``delay`` on, is ``resample(whole signal)`` bit for bit, however the signal was cut into pushes.  The first ``delay`` samples of a fresh stream
+    are the filter's pre-ringing against the silence before it, not zeros: a caller that lines outputs up with inputs drops them.  The state is
+    the last D o + width input samples of every stream; ``reset()`` makes the streams fresh again."""
+
+    def __init__(self, resample: Resample, batch: int):
+        if resample.orig_freq == resample.new_freq:
+            raise ValueError("equal rates need no stream")
+        if batch < 1:
+            raise ValueError("batch must be positive")
+        self.resample, self.batch = resample, int(batch)
+        self.history = resample.delay_blocks * resample.o + resample.width
+        self.delay = resample.delay_blocks * resample.n
+        self.state = None
+        self._dtype = torch.float32
+
+    def reset(self) -> None:
+        if self.state is not None:
+            self.state.zero_()
+
+    def push(self, chunk: torch.Tensor) -> torch.Tensor:
+        r = self.resample
+        if not chunk.is_cuda:
+            raise RuntimeError("ResampleStream: expected a CUDA tensor (this package has no CPU path)")
+        if chunk.dtype not in (torch.float32, torch.int16):
+            raise TypeError(f"ResampleStream: expected torch.float32 or torch.int16, got {chunk.dtype}")
+        if chunk.dim() != 2 or chunk.shape[0] != self.batch or chunk.shape[1] % r.o != 0:
+            raise ValueError(f"a push is ({self.batch}, k * {r.o}) samples, whole blocks; got {tuple(chunk.shape)}")
+        if chunk.shape[1] == 0:          # nothing arrived (a stream front end that is still priming emits (B, 0)): nothing is owed, the state stays
+            return torch.empty(self.batch, 0, dtype=chunk.dtype, device=chunk.device)
+        if self.state is None:
+            self.state = torch.zeros(self.batch, self.history, dtype=torch.float32, device=chunk.device)
+        elif self.state.device != chunk.device:
+            raise RuntimeError(f"the streams live on {self.state.device}")
+        self._dtype = chunk.dtype
+        blocks = chunk.shape[1] // r.o
+        x, xs = Resample._rows(chunk)
+        out = torch.empty(self.batch, blocks * r.n, dtype=chunk.dtype, device=chunk.device)
+        s16 = int(chunk.dtype == torch.int16)
+        with torch.cuda.device(chunk.device):
+            r.lib.check(r.lib.dn_resample_push(r.handle(chunk.device), self.state.data_ptr(), x.data_ptr(), s16, out.data_ptr(), s16, self.batch, blocks,
+                                               xs, blocks * r.n, _stream_ptr(chunk.device)))
+        return out
+
+    def flush(self) -> torch.Tensor:
+        """pushes D blocks of zeros (in the dtype of the last push): the samples still owed for what has been pushed"""
+        if self.state is None:
+            raise RuntimeError("nothing has been pushed")
+        return self.push(torch.zeros(self.batch, self.resample.delay_blocks * self.resample.o, dtype=self._dtype, device=self.state.device))

@@ -32,6 +32,8 @@
  *   dn_sessions_*                       app3.py:123-250  one DenoisingAudioProcessor per session: slots that join, leave
  *                                       and push hops on their own, batched per tick; sessions exported to and
  *                                       imported from self-contained records (move, resume, resize a pool)
+ *   dn_resample_*                       utils.py:48-49, app.py:181  torchaudio Resample / librosa.resample: audio at another
+ *                                       rate than the plan's, whole signals and streams
  *   dn_pipe_*                           app3.py:167-250  the same hop, consecutive hops software-pipelined in one launch per hop
  *                                       (dn_pipe_stream_*: the steady-state recv loop with its per-stream buffers)
  *
@@ -598,6 +600,67 @@ size_t dn_sessions_record_bytes(const dn_sessions* s);
 int dn_sessions_export(dn_sessions* s, const int32_t* ids, int32_t n, void* records, void* stream);
 int dn_sessions_import(dn_sessions* s, const int32_t* ids, int32_t n, const void* records, const uint64_t* stream_ids,
                        void* stream);
+
+/* ---- Sample-rate conversion ---------------------------------------------------------------------------------
+ * torchaudio.transforms.Resample (2.6.0) on the device: the transform the reference builds as Resample(44100, SR) and
+ * Resample(SR, 44100) at utils.py:48-49 and replaces with librosa.resample at app.py:181.  Audio that arrives at another rate
+ * than the plan's (8 kHz files, 44.1 kHz uploads, 48 kHz WebRTC) is converted where it already is, float32 or int16 PCM.
+ *
+ * Arithmetic (restated from torchaudio's _get_sinc_resample_kernel / _apply_sinc_resample_kernel; parity with torchaudio itself
+ * is unpinned).  With g = gcd(orig_freq, new_freq), o = orig_freq / g, n = new_freq / g:
+ *   base = min(o, n) * rolloff      width = ceil(lowpass_filter_width * o / base)      taps KW = 2 width + o
+ *   k[p][j], p in [0, n), j in [0, KW), in double, rounded once to float32:
+ *     t = (-p / n + (j - width) / o) * base, clamped to +-lowpass_filter_width
+ *     k = sinc(pi t) * cos^2(t pi / lowpass_filter_width / 2) * base / o          (sinc(0) = 1; the Hann window)
+ *   y[q n + p] = sum_j k[p][j] * xz[q o + j - width],  xz = x with zeros outside [0, L);  ceil(n L / o) samples out
+ * On the device one output is ONE chain acc = fmaf(k[p][j], x, acc) over j ascending from acc = 0, in every kernel form and in
+ * both entry points; the bit-for-bit statements below rest on that order.
+ *
+ * cfg: equal rates, a rate < 1, lowpass_filter_width < 1 or rolloff outside (0, 1]: DN_ERR_INVALID.  o or n > 1024, or
+ * n * KW > 2^19 floats: DN_ERR_UNSUPPORTED (the message names the limits).
+ * kernel [host][n][KW] or NULL: a caller-built table (torchaudio's Kaiser window, anything else) in place of the Hann table
+ * above, as dn_dsp_create takes fb / pinv / window; its geometry is still cfg's (read it back from a handle created with NULL).
+ * The handle lives on the current HIP device, is immutable and may be shared by threads. */
+typedef struct dn_resampler dn_resampler;
+typedef struct dn_resample_cfg {
+    int32_t orig_freq;
+    int32_t new_freq;
+    int32_t lowpass_filter_width; /* torchaudio's default: 6 */
+    double rolloff;               /* torchaudio's default: 0.99 */
+} dn_resample_cfg;
+int dn_resample_create(const dn_resample_cfg* cfg, const float* kernel, dn_resampler** out);
+void dn_resample_destroy(dn_resampler* r);
+/* o, n, width, taps (KW) and delay_blocks (D = ceil(width / o)); any of the pointers may be NULL */
+int dn_resample_geometry(const dn_resampler* r, int32_t* o, int32_t* n, int32_t* width, int32_t* taps, int32_t* delay_blocks);
+/* kernel [host][n][KW]: the float32 table as held */
+int dn_resample_get_kernel(const dn_resampler* r, float* kernel);
+/* ceil(n L / o); 0 for a null handle or L < 1 */
+int64_t dn_resample_out_len(const dn_resampler* r, int64_t L);
+
+/* The whole-signal form: B rows of L samples -> B rows of dn_resample_out_len(r, L) samples, one launch; no workspace, no
+ * allocation, no synchronisation.
+ *   x [dev][B][x_stride]  float32, or int16 PCM (x / 32767) when in_s16; x_stride >= L elements
+ *   y [dev][B][y_stride]  float32, or int16 (clip to +-1, * 32767, truncate) when out_s16; y_stride >= the output length
+ * (the int16 conventions of dn_stream_step, P12).  Rows need no alignment; rows that start on 16-byte (x) and 8-byte (y; 4 for
+ * int16) boundaries are moved in wider accesses.  y must not overlap x.  L >= 1 and at most 2^30 samples in and out;
+ * B == 0 returns DN_OK.  A row followed by zeros gives the row's own outputs followed by more: the extra terms are k * 0. */
+int dn_resample(const dn_resampler* r, const void* x, int32_t in_s16, void* y, int32_t out_s16, int32_t B, int64_t L,
+                int64_t x_stride, int64_t y_stride, void* stream);
+
+/* The streaming form: every push brings `blocks` >= 1 blocks of o samples per stream and emits blocks * n.
+ *   state [dev][B][H] float32, H = D o + width, dn_resample_state_bytes(r, B) bytes (0 for a null handle or B < 1): the last H
+ *   input samples of each stream, owned by the caller as ring / ola are for dn_stream_step.  All zeros is a fresh stream.
+ *   x [dev][B][x_stride], x_stride >= blocks * o;   y [dev][B][y_stride], y_stride >= blocks * n;   formats as above.
+ * The concatenated output of a stream is the whole-signal output of (zeros, then the stream) delayed by D blocks:
+ *   concat(pushes of L = whole blocks of samples, then a push of D blocks of zeros)[D n : D n + ceil(n L / o)]
+ * equals dn_resample of the same L samples bit for bit, however the samples were cut into pushes.  The first D n samples a fresh
+ * stream emits are the filter's pre-ringing against the silence before it, not zeros: a caller that wants output sample 0 lined
+ * up with input sample 0 drops them.
+ * Two launches, in stream order: the outputs from [state | x] (every workgroup reads the old state), then the new state.
+ * Every argument of both forms is checked before the first launch: a refused call leaves y and state untouched. */
+size_t dn_resample_state_bytes(const dn_resampler* r, int32_t B);
+int dn_resample_push(const dn_resampler* r, float* state, const void* x, int32_t in_s16, void* y, int32_t out_s16, int32_t B,
+                     int64_t blocks, int64_t x_stride, int64_t y_stride, void* stream);
 
 const char* dn_last_error(void);
 int dn_abi_version(void);
