@@ -529,6 +529,16 @@ size_t dn_clip_workspace_bytes_ex(const dn_dsp* d, int32_t B, int32_t N, uint32_
     return base == 0 || !(flags & DN_PHASE_FROM_INPUT) ? base : base + phasor_bytes(d, (size_t)B * (size_t)N);
 }
 
+// the rows of a call's workspace, F frames from `rows` on: frame rows | mel | residual | peak, then the phasor rows of an input-phase call (the
+// uniform call's layout, F = B x N; a ragged call's behind its table)
+static void clip_carve(dn::ClipArgs& a, const dn_dsp* d, void* rows, size_t F, uint32_t flags) {
+    const int M = d->cfg.n_mels;
+    a.frames = F;
+    a.fr = static_cast<float*>(rows); a.fr_stride = clip_row_floats(d);
+    a.mel = a.fr + F * a.fr_stride; a.diff = a.mel + F * 3 * M; a.peak = a.diff + F * 3 * M;
+    if (flags & DN_PHASE_FROM_INPUT) a.phas = reinterpret_cast<float*>(static_cast<char*>(rows) + dn_clip_workspace_bytes(d, 1, (int32_t)F));
+}
+
 int dn_clip_process(const dn_model* m, const dn_dsp* d, const void* hops_in, int32_t in_s16, float* ring, float* ola, float* hx, void* hops_out, int32_t out_s16, const float* init_angles,
                     uint64_t seed, uint64_t stream_id0, int32_t n_iter, float momentum, void* workspace, int32_t B, int32_t N, uint32_t flags, void* stream) {
     // every argument is validated before the first launch, so a failed call leaves ring, ola and hx untouched
@@ -547,10 +557,7 @@ int dn_clip_process(const dn_model* m, const dn_dsp* d, const void* hops_in, int
     a.hops_in = hops_in; a.in_s16 = in_s16 != 0; a.ring = ring; a.ola = ola; a.hx = hx; a.hops_out = hops_out; a.out_s16 = out_s16 != 0;
     a.init = init_angles; a.seed = seed; a.sid0 = stream_id0; a.n_iter = n_iter;
     a.C = C; a.B = B; a.N = N; a.n_fft = d->cfg.n_fft; a.n_mels = M;
-    a.frames = (size_t)B * (size_t)N;
-    a.fr = static_cast<float*>(workspace); a.fr_stride = clip_row_floats(d);
-    a.mel = a.fr + a.frames * a.fr_stride; a.diff = a.mel + a.frames * 3 * M; a.peak = a.diff + a.frames * 3 * M;
-    if (flags & DN_PHASE_FROM_INPUT) a.phas = reinterpret_cast<float*>(static_cast<char*>(workspace) + dn_clip_workspace_bytes(d, B, N));
+    clip_carve(a, d, workspace, (size_t)B * (size_t)N, flags);
     a.per_stream = d->cfg.n_fft == 1024 && ((gl & DN_CLIP_GL_PER_STREAM) || (gl == 0 && (long)a.frames >= dn::kClipGlwAutoFrames));
     dn::launch_clip(d->view, bs->view_dev.get(), a, (flags & DN_CONV_BF16) != 0, as_stream(stream));
     return check_launch("dn_clip_process");
@@ -606,16 +613,12 @@ int dn_clip_process_ragged(const dn_model* m, const dn_dsp* d, const void* hops_
         f0[b] = frame0 ? frame0[b] : 0;
     }
     DN_HIP(hipMemcpyAsync(workspace, host.data(), table, hipMemcpyHostToDevice, as_stream(stream)));
-    char* rows = static_cast<char*>(workspace) + clip_table_bytes(B);
     a.off = static_cast<const int*>(workspace);
     a.frame0 = reinterpret_cast<const uint64_t*>(static_cast<const char*>(workspace) + off_bytes);
     a.hops_in = hops_in; a.in_s16 = in_s16 != 0; a.ring = ring; a.ola = ola; a.hx = hx; a.hops_out = hops_out; a.out_s16 = out_s16 != 0;
     a.init = init_angles; a.seed = seed; a.sid0 = stream_id0; a.n_iter = n_iter;
     a.C = C; a.B = B; a.N = 0; a.n_fft = d->cfg.n_fft; a.n_mels = M;
-    a.frames = (size_t)F;
-    a.fr = reinterpret_cast<float*>(rows); a.fr_stride = clip_row_floats(d);
-    a.mel = a.fr + a.frames * a.fr_stride; a.diff = a.mel + a.frames * 3 * M; a.peak = a.diff + a.frames * 3 * M;
-    if (flags & DN_PHASE_FROM_INPUT) a.phas = reinterpret_cast<float*>(rows + dn_clip_workspace_bytes(d, 1, (int32_t)F));
+    clip_carve(a, d, static_cast<char*>(workspace) + clip_table_bytes(B), (size_t)F, flags);
     a.per_stream = d->cfg.n_fft == 1024 && ((gl & DN_CLIP_GL_PER_STREAM) || (gl == 0 && (long)a.frames >= dn::kClipGlwAutoFrames));
     dn::launch_clip(d->view, bs->view_dev.get(), a, (flags & DN_CONV_BF16) != 0, as_stream(stream));
     return check_launch("dn_clip_process_ragged");

@@ -6,8 +6,6 @@
 
 namespace {
 
-size_t slot_floats(const dn_dsp* d, int32_t B) { return (size_t)B * (6 * (size_t)d->cfg.n_mels + 1 + dn::kSlotMeta + 3 * ((size_t)d->cfg.n_fft / 2 + 1)); }
-
 // the head start a one-hop pipe runs with unless told otherwise (measured optima; n_fft 512 takes 1024's, not swept yet; none above 256 streams, none on a deep pipe)
 int default_head_start(const dn_pipe* p) { return p->depth == 1 && p->B <= 256 ? (p->d->cfg.n_fft == 1536 ? 12 : 8) : 0; }
 
@@ -50,9 +48,9 @@ int dn_pipe_create(const dn_model* m, const dn_dsp* d, int32_t B, uint32_t flags
     p->bf16 = (flags & DN_CONV_BF16) != 0;
     p->phase_in = (flags & DN_PHASE_FROM_INPUT) != 0;
     DN_TRY(build_bias(m, p->C, &p->bs));
-    p->slot_floats = (slot_floats(d, B) + 63) & ~size_t(63);
+    p->slot_floats = (dn::SlotLayout(B, d->cfg.n_mels, d->cfg.n_fft / 2 + 1).floats + 63) & ~size_t(63);
     p->init_elems = (size_t)B * 3 * (d->cfg.n_fft / 2 + 1);
-    p->state_elems = (size_t)B * 3 * (2 * ((size_t)d->cfg.n_fft / 128) + 2) * 64;       // n_fft / 128 complex values per lane
+    p->state_elems = (size_t)B * dn::parked_elems(d->cfg.n_fft);
     static_assert(sizeof(dn::PipeCtl) <= 256, "the control block fits its allocation");
     hipError_t e = p->ctl.alloc_zeroed(256);
     if (e == hipSuccess) e = p->scratch.alloc(p->n_slots * p->slot_floats * sizeof(float));

@@ -19,15 +19,6 @@ __global__ __launch_bounds__(kHopPipeThreads) void clip_invmel_kernel(DspDev d, 
 // of one stream; job 0 is everything that touches the stream's overlap-add line (out_0, out_1, the new line: the pair's old samples are in
 // registers before the thread rewrites them, and no other thread reads them), job j >= 1 is out_{j+1}.
 constexpr int kClipFoldThreads = 256;
-__device__ __forceinline__ void clip_emit(void* out, int s16, size_t at, v2f v) {
-    if (s16) {
-        const float c0 = fminf(fmaxf(v[0], -1.0f), 1.0f) * 32767.0f, c1 = fminf(fmaxf(v[1], -1.0f), 1.0f) * 32767.0f;   // np.clip, * iinfo(int16).max
-        // astype(int16): truncation; the pair goes out as one 4-byte store
-        *reinterpret_cast<unsigned int*>(static_cast<short*>(out) + at) = (unsigned int)(unsigned short)(short)c0 | ((unsigned int)(unsigned short)(short)c1 << 16);
-    } else {
-        *reinterpret_cast<v2f*>(static_cast<float*>(out) + at) = v;
-    }
-}
 // A ragged call (a.off non-null) has one job per frame instead, found from off alone: thread u owns pair u % pairs of frame f = u / pairs, hop i of
 // the stream b that owns f (clip_owner; f differs within a workgroup here, so these loads are per lane).  Frame 0 of a stream is its job 0, frame i
 // in 1 .. N_b - 2 is job i (out_{i+1}), and the stream's last frame idles when N_b > 1.  The jobs themselves are the ones below, N = N_b.
@@ -51,27 +42,26 @@ __global__ __launch_bounds__(kClipFoldThreads) void clip_fold_kernel(ClipArgs a)
     }
     const int n = 2 * m;
     auto pair = [&](size_t i, int off) { return *reinterpret_cast<const v2f*>(a.fr + (f0 + i) * a.fr_stride + off + n); };
-    auto fma2 = [](v2f e, float s, v2f c) { return mk2(fmaf(e[0], s, c[0]), fmaf(e[1], s, c[1])); };
     const v2f zero = mk2(0.0f, 0.0f);
     const size_t out0 = f0 * hop + n;          // the pair in hop 0 of the stream's output row
     if (j == 0) {
         float* orow = a.ola + b * (size_t)a.n_fft;
         const v2f lo = *reinterpret_cast<const v2f*>(orow + n), hi = *reinterpret_cast<const v2f*>(orow + hop + n);
-        clip_emit(a.hops_out, a.out_s16, out0, lo);
-        const v2f first = fma2(pair(0, 0), a.peak[f0], hi);          // hop 0's frame on the old line
+        pcm_store_pair(a.hops_out, a.out_s16, out0, lo);
+        const v2f first = ola_term(pair(0, 0), a.peak[f0], hi);          // hop 0's frame on the old line
         v2f nlo = first;
         if (N > 1) {
-            clip_emit(a.hops_out, a.out_s16, out0 + hop, first);
+            pcm_store_pair(a.hops_out, a.out_s16, out0 + hop, first);
             const size_t l = (size_t)N - 1;
-            nlo = fma2(pair(l, 0), a.peak[f0 + l], fma2(pair(l - 1, hop), a.peak[f0 + l - 1], zero));
+            nlo = ola_term(pair(l, 0), a.peak[f0 + l], ola_term(pair(l - 1, hop), a.peak[f0 + l - 1], zero));
         }
         const size_t l = (size_t)N - 1;
-        const v2f nhi = fma2(pair(l, hop), a.peak[f0 + l], zero);
+        const v2f nhi = ola_term(pair(l, hop), a.peak[f0 + l], zero);
         *reinterpret_cast<v2f*>(orow + n) = nlo;
         *reinterpret_cast<v2f*>(orow + hop + n) = nhi;
     } else {
         const size_t i = j + 1;
-        clip_emit(a.hops_out, a.out_s16, out0 + i * hop, fma2(pair(i - 1, 0), a.peak[f0 + i - 1], fma2(pair(i - 2, hop), a.peak[f0 + i - 2], zero)));
+        pcm_store_pair(a.hops_out, a.out_s16, out0 + i * hop, ola_term(pair(i - 1, 0), a.peak[f0 + i - 1], ola_term(pair(i - 2, hop), a.peak[f0 + i - 2], zero)));
     }
 }
 

@@ -101,12 +101,7 @@ __global__ __launch_bounds__(kHopPipeThreads) void clip_analysis_kernel(DspDev d
         if (i == 0 && j4 < kHop4) v = r4[kHop4 + j4];
         else {
             const size_t at = in0 + (i == 0 ? 0 : (i - 1) * kHop) + 4 * (size_t)(i == 0 ? j4 - kHop4 : j4);
-            if (a.in_s16) {      // int16 -> float32 / iinfo(int16).max   (app3.py:172, as ring_shift)
-                const short4 q = *reinterpret_cast<const short4*>(static_cast<const short*>(a.hops_in) + at);
-                v = make_float4((float)q.x / 32767.0f, (float)q.y / 32767.0f, (float)q.z / 32767.0f, (float)q.w / 32767.0f);
-            } else {
-                v = *reinterpret_cast<const float4*>(static_cast<const float*>(a.hops_in) + at);
-            }
+            v = pcm_load4(a.hops_in, a.in_s16, at);
         }
         reinterpret_cast<float4*>(row)[j4] = v;
     }

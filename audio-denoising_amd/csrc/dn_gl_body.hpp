@@ -5,6 +5,7 @@
 #include "dn_internal.hpp"
 #include "dn_wavefft.hpp"
 #include "dn_invmel_body.hpp"
+#include "dn_pcm.hpp"
 
 namespace dn {
 
@@ -246,18 +247,20 @@ __device__ __forceinline__ void gl_body(char* smem, const DspDev& d, const float
 
     // The iteration loop is instantiated once per column (W is a compile-time constant inside): the overlap-add
     // stores and every other column-dependent choice become straight-line code instead of per-value predicates.
-    v2f* mystate = state != nullptr ? state + ((b * 3 + w) * (2 * kNV + 2)) * 64 + lane : nullptr;
+    using P = Parked<NFFT>;
+    static_assert(P::kNV == kNV, "the parked chain holds a row per register of the lane's state");
+    v2f* mystate = state != nullptr ? P::column(state, b, w, lane) : nullptr;
     auto iterate = [&](auto wc) {
     constexpr int W = decltype(wc)::value;
     v2f v[kNV], xlo[kNP], xhi[kNP], xmid, rlo[kNP], rhi[kNP], rmid;
     if (it_begin > 0) {
 #pragma unroll
         for (int t = 0; t < kNP; ++t) {
-            xlo[t] = mystate[64 * t]; xhi[t] = mystate[64 * (kNP + t)];
-            plo[t] = mystate[64 * (kNV + 1 + t)]; phi[t] = mystate[64 * (kNV + 1 + kNP + t)];
+            xlo[t] = mystate[P::xlo(t)]; xhi[t] = mystate[P::xhi(t)];
+            plo[t] = mystate[P::plo(t)]; phi[t] = mystate[P::phi(t)];
         }
-        xmid = mystate[64 * kNV];
-        pmid = mystate[64 * (2 * kNV + 1)];
+        xmid = mystate[P::xmid()];
+        pmid = mystate[P::pmid()];
     } else {
 #pragma unroll
         for (int t = 0; t < kNP; ++t) {
@@ -271,11 +274,11 @@ __device__ __forceinline__ void gl_body(char* smem, const DspDev& d, const float
         if (it == it_stop) {          // hand the chain over (uniform)
 #pragma unroll
             for (int t = 0; t < kNP; ++t) {
-                mystate[64 * t] = xlo[t]; mystate[64 * (kNP + t)] = xhi[t];
-                mystate[64 * (kNV + 1 + t)] = plo[t]; mystate[64 * (kNV + 1 + kNP + t)] = phi[t];
+                mystate[P::xlo(t)] = xlo[t]; mystate[P::xhi(t)] = xhi[t];
+                mystate[P::plo(t)] = plo[t]; mystate[P::phi(t)] = phi[t];
             }
-            mystate[64 * kNV] = xmid;
-            mystate[64 * (2 * kNV + 1)] = pmid;
+            mystate[P::xmid()] = xmid;
+            mystate[P::pmid()] = pmid;
             break;
         }
         // ---- istft of X = angles * magnitude: Hermitian merge, inverse FFT, synthesis window, overlap-add lines
@@ -319,15 +322,8 @@ __device__ __forceinline__ void gl_body(char* smem, const DspDev& d, const float
                 for (int r = 0; r < kR; ++r) {
                     const int n = tid + kGlThreads * r;
                     if (n < kNR) {
-                        orow[n] = fmaf((y1[n] + yo[n]) * d.inv_env[n], sc, nxt[r]);     // (the contraction the compiler makes anyway, spelled out: dn_glw_body.hpp must round alike)
-                        if (n < kNR / 2) {
-                            if (out_s16) {
-                                const float c = fminf(fmaxf(cur[r], -1.0f), 1.0f) * 32767.0f;      // np.clip, * iinfo(int16).max
-                                static_cast<short*>(hop_out)[b * (kNR / 2) + n] = (short)c;          // astype(int16): truncation
-                            } else {
-                                static_cast<float*>(hop_out)[b * (kNR / 2) + n] = cur[r];
-                            }
-                        }
+                        orow[n] = ola_term(y1[n] + yo[n], d.inv_env[n], sc, nxt[r]);
+                        if (n < kNR / 2) pcm_store(hop_out, out_s16, b, kNR / 2, n, cur[r]);
                     }
                 }
             }

@@ -153,8 +153,8 @@ __device__ __forceinline__ void glw_body(char* smem, const DspDev& d, const floa
     // segment format, per stream, rows of 64 lanes: 3 x kNP float4 rows (column c: plo pairs, then phi pairs), kNV / 2 float4 rows (signal pairs),
     // then three v2f rows (pmid)
     constexpr int kPrevRows = 3 * kNP, kSigRows = kNV / 2, kSegBytes = (kPrevRows + kSigRows) * 1024 + 3 * 512;
-    static_assert(kNP % 2 == 0 && kSegBytes <= 8 * 3 * (2 * kNV + 2) * 64, "a parked segment fits the slot gl_body's format needs");
-    char* seg = state != nullptr ? reinterpret_cast<char*>(state) + b * (size_t)(8 * 3 * (2 * kNV + 2) * 64) : nullptr;
+    static_assert(kNP % 2 == 0 && kSegBytes <= 8 * parked_elems(NFFT), "a parked segment fits the slot gl_body's format needs");
+    char* seg = state != nullptr ? reinterpret_cast<char*>(state) + b * (8 * parked_elems(NFFT)) : nullptr;
     auto park_segment = [&]() {
         float4* q = reinterpret_cast<float4*>(seg) + lane;
 #pragma unroll
@@ -208,14 +208,15 @@ __device__ __forceinline__ void glw_body(char* smem, const DspDev& d, const floa
         } else if (resume == kGlwFromX) {
 #pragma unroll
             for (int c = 0; c < 3; ++c) {
-                const v2f* st = state + ((b * 3 + c) * (2 * kNV + 2)) * 64 + lane;
+                using P = Parked<NFFT>;
+                const v2f* st = P::column(state, b, c, lane);
 #pragma unroll
                 for (int t = 0; t < kNP; ++t) {
-                    xlo[c][t] = st[64 * t]; xhi[c][t] = st[64 * (kNP + t)];
-                    plo[c][t] = st[64 * (kNV + 1 + t)]; phi[c][t] = st[64 * (kNV + 1 + kNP + t)];
+                    xlo[c][t] = st[P::xlo(t)]; xhi[c][t] = st[P::xhi(t)];
+                    plo[c][t] = st[P::plo(t)]; phi[c][t] = st[P::phi(t)];
                 }
-                xmid[c] = st[64 * kNV];
-                pmid[c] = st[64 * (2 * kNV + 1)];
+                xmid[c] = st[P::xmid()];
+                pmid[c] = st[P::pmid()];
             }
         } else {
             if (init != nullptr) {
@@ -384,20 +385,10 @@ __device__ __forceinline__ void glw_body(char* smem, const DspDev& d, const floa
             const int n = 2 * (lane + 64 * t);
             const v2f e = *reinterpret_cast<const v2f*>(d.inv_env + n);
             const v2f old = t < kHalf ? nxt[t % kHalf] : mk2(0.0f, 0.0f);
-            *reinterpret_cast<v2f*>(orow + n) = mk2(fmaf(snew[t][0] * e[0], sc, old[0]), fmaf(snew[t][1] * e[1], sc, old[1]));     // as gl_body
+            *reinterpret_cast<v2f*>(orow + n) = ola_term(snew[t], e, sc, old);
         }
 #pragma unroll
-        for (int t = 0; t < kHalf; ++t) {
-            const int n = 2 * (lane + 64 * t);
-            if (out_s16) {
-                const float c0 = fminf(fmaxf(cur[t][0], -1.0f), 1.0f) * 32767.0f, c1 = fminf(fmaxf(cur[t][1], -1.0f), 1.0f) * 32767.0f;   // np.clip, * iinfo(int16).max
-                // astype(int16): truncation; the pair goes out as ONE 4-byte store (the buffer may be host memory behind PCIe)
-                const unsigned int pair = (unsigned int)(unsigned short)(short)c0 | ((unsigned int)(unsigned short)(short)c1 << 16);
-                *reinterpret_cast<unsigned int*>(static_cast<short*>(hop_out) + b * (kNR / 2) + n) = pair;
-            } else {
-                *reinterpret_cast<v2f*>(static_cast<float*>(hop_out) + b * (kNR / 2) + n) = cur[t];
-            }
-        }
+        for (int t = 0; t < kHalf; ++t) pcm_store_pair(hop_out, out_s16, b, kNR / 2, 2 * (lane + 64 * t), cur[t]);
     }
 }
 

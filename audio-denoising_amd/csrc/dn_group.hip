@@ -70,12 +70,11 @@ __global__ __launch_bounds__(kHopPipeThreads, 2) void group_kernel(DspDev d, con
             const int s = slot_behind(slot_next, (int)pending - j, a.n_slots);
             const float* slot = a.slots + (size_t)s * a.slot_stride;
             const uint32_t* meta = reinterpret_cast<const uint32_t*>(slot + sl.meta) + kSlotMeta * b;
-            const v2f* init = meta[0] ? reinterpret_cast<const v2f*>(a.slot_init + (size_t)s * a.init_stride) : nullptr;
-            const uint64_t seed = (uint64_t)meta[1] | ((uint64_t)meta[2] << 32);
-            const uint64_t sid0 = (uint64_t)meta[3] | ((uint64_t)meta[4] << 32);
-            const int n_iter = __builtin_amdgcn_readfirstlane((int)meta[6]);
-            const float mom = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane((int)meta[7]));
-            float* gl_out = reinterpret_cast<float*>((uint64_t)meta[8] | ((uint64_t)meta[9] << 32));
+            const v2f* init = FrameMeta::load_has_init(meta) ? reinterpret_cast<const v2f*>(a.slot_init + (size_t)s * a.init_stride) : nullptr;
+            const uint64_t seed = FrameMeta::load_seed(meta), sid0 = FrameMeta::load_sid0(meta);
+            const int n_iter = FrameMeta::load_n_iter(meta);          // (it0 is 0: no head start here)
+            const float mom = FrameMeta::load_mom(meta);
+            float* gl_out = FrameMeta::load_out(meta);
 #ifdef DN_GLW_PRIO
             __builtin_amdgcn_s_setprio(DN_GLW_PRIO);          // (experiment knob: measured below)
 #endif
@@ -112,16 +111,10 @@ __global__ __launch_bounds__(kHopPipeThreads, 2) void group_kernel(DspDev d, con
                         if (has) {
                             emit = lo[r];
                             const v2f p0 = *reinterpret_cast<const v2f*>(line + 2 * m), p1 = *reinterpret_cast<const v2f*>(line + 2 * m + kHop);
-                            lo[r] = mk2(fmaf(p0[0], sc, hi[r][0]), fmaf(p0[1], sc, hi[r][1]));
-                            hi[r] = mk2(fmaf(p1[0], sc, 0.0f), fmaf(p1[1], sc, 0.0f));
+                            lo[r] = ola_term(p0, sc, hi[r]);
+                            hi[r] = ola_term(p1, sc, mk2(0.0f, 0.0f));
                         }
-                        const size_t at = (size_t)i * (size_t)a.hop_out_stride + bs * kHop + 2 * m;
-                        if (a.out_s16) {
-                            const float c0 = fminf(fmaxf(emit[0], -1.0f), 1.0f) * 32767.0f, c1 = fminf(fmaxf(emit[1], -1.0f), 1.0f) * 32767.0f;   // app3.py:244-245
-                            *reinterpret_cast<unsigned int*>(static_cast<short*>(a.hop_out) + at) = (unsigned int)(unsigned short)(short)c0 | ((unsigned int)(unsigned short)(short)c1 << 16);
-                        } else {
-                            *reinterpret_cast<v2f*>(static_cast<float*>(a.hop_out) + at) = emit;
-                        }
+                        pcm_store_pair(a.hop_out, a.out_s16, (size_t)i * (size_t)a.hop_out_stride + bs * kHop + 2 * m, emit);
                     }
                 }
                 if (P > 0) {
@@ -171,17 +164,7 @@ __global__ __launch_bounds__(kHopPipeThreads, 2) void group_kernel(DspDev d, con
             if (tid == 0) {
                 uint32_t* meta = reinterpret_cast<uint32_t*>(slot + sl.meta) + kSlotMeta * b;
                 const uint64_t seed = a.seed + frames + (unsigned long long)q;
-                meta[0] = (PHIN || a.init_in != nullptr) ? 1u : 0u;
-                meta[1] = (uint32_t)seed;
-                meta[2] = (uint32_t)(seed >> 32);
-                meta[3] = (uint32_t)a.sid0;
-                meta[4] = (uint32_t)(a.sid0 >> 32);
-                meta[5] = 0u;
-                meta[6] = (uint32_t)a.n_iter;
-                meta[7] = __builtin_bit_cast(uint32_t, a.mom);
-                const uint64_t dst = reinterpret_cast<uint64_t>(STREAM ? nullptr : a.gl_out + (size_t)h * (size_t)a.out_stride);
-                meta[8] = (uint32_t)dst;
-                meta[9] = (uint32_t)(dst >> 32);
+                FrameMeta{PHIN || a.init_in != nullptr, seed, a.sid0, 0, a.n_iter, a.mom, STREAM ? nullptr : a.gl_out + (size_t)h * (size_t)a.out_stride}.store(meta);
             }
             if (!PHIN && a.init_in != nullptr) {
                 const float2* src = reinterpret_cast<const float2*>(a.init_in + (size_t)h * (size_t)a.init_in_stride) + b * 3 * kBins;

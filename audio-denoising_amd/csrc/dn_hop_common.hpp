@@ -1,10 +1,11 @@
 // dn_hop_common.hpp -- what the fused launches (dn_hop.hip: hop_kernel, frame_kernel; dn_group.hip: group_kernel) share: workgroup shape, LDS budget,
-// the ring shift of the streaming front end and the layout of a pipe's scratch slots.
+// and the ring shift of the streaming front end (the layout of a pipe's scratch slots: dn_internal.hpp).
 #pragma once
 #include "dn_cell_body.hpp"
 #include "dn_gl_body.hpp"
 #include "dn_glw_body.hpp"
 #include "dn_invmel_body.hpp"
+#include "dn_pcm.hpp"
 #include "dn_stft_body.hpp"
 
 namespace dn {
@@ -39,12 +40,9 @@ __device__ __forceinline__ void ring_shift(float* ring, const void* hop_in, int 
         if (i4 < kLine4 - kHop4) v[r] = r4[i4 + kHop4];
         else if (i4 < kLine4) {
             const int j4 = i4 - (kLine4 - kHop4);
-            if (in_s16) {      // int16 -> float32 / iinfo(int16).max   (app3.py:172)
-                const short4 q = reinterpret_cast<const short4*>(static_cast<const short*>(hop_in) + b * (kNR / 2))[j4];
-                v[r] = make_float4((float)q.x / 32767.0f, (float)q.y / 32767.0f, (float)q.z / 32767.0f, (float)q.w / 32767.0f);
-            } else {
-                v[r] = reinterpret_cast<const float4*>(static_cast<const float*>(hop_in) + b * (kNR / 2))[j4];
-            }
+            // pcm_load4, spelled out: with the row's offset formed once in front of both forms the one-launch kernels compile to other code
+            if (in_s16) v[r] = pcm_f32(reinterpret_cast<const short4*>(static_cast<const short*>(hop_in) + b * (kNR / 2))[j4]);
+            else v[r] = reinterpret_cast<const float4*>(static_cast<const float*>(hop_in) + b * (kNR / 2))[j4];
         }
     }
     __syncthreads();
@@ -55,17 +53,6 @@ __device__ __forceinline__ void ring_shift(float* ring, const void* hop_in, int 
     }
     __syncthreads();
 }
-
-// offsets (in floats) of the parts of a scratch slot.  meta: kSlotMeta u32 per stream, written by the frame's front workgroup and read by its
-// Griffin-Lim workgroup in the next launch -- everything the pending hop is finished with is the FRAME's own, not the next call's:
-//   [0] has injected phases  [1,2] Griffin-Lim seed  [3,4] stream id of stream 0  [5] head-start iterations already run
-//   [6] n_iter  [7] momentum / (1 + momentum) (bits)  [8,9] where the frame goes (frame mode: the `out` of its dn_pipe_submit)
-struct SlotLayout {
-    size_t diff, peak, meta, lin;
-    __host__ __device__ SlotLayout(int B, int M, int K) {
-        diff = (size_t)B * 3 * M; peak = 2 * diff; meta = peak + B; lin = meta + kSlotMeta * (size_t)B; (void)K;
-    }
-};
 
 // A zero the compiler cannot see through.  dn_group.hip adds it, once per hop, to the pointers through which the front half reads the plan's and the
 // model's views in device memory: loads through a pointer that changes every iteration are not loop-invariant, so a loop over large inlined stages

@@ -122,14 +122,11 @@ __global__ __launch_bounds__(kHopPipeThreads, FRONT ? kFrontPerCu : (NFFT == 153
                     const int s = slot_behind(slot_next, 1 + j, a.n_slots);
                     const float* slot = a.slots + (size_t)s * a.slot_stride;
                     const uint32_t* meta = reinterpret_cast<const uint32_t*>(slot + sl.meta) + kSlotMeta * b;
-                    const v2f* init = meta[0] ? reinterpret_cast<const v2f*>(a.slot_init + (size_t)s * a.init_stride) : nullptr;
-                    const uint64_t seed = (uint64_t)meta[1] | ((uint64_t)meta[2] << 32);
-                    const uint64_t sid0 = (uint64_t)meta[3] | ((uint64_t)meta[4] << 32);
-                    // (the slot words come back through the vector memory path: readfirstlane tells the compiler they are wave-uniform, so the
-                    // iteration loop keeps a scalar trip count and a scalar branch)
-                    const int it0 = __builtin_amdgcn_readfirstlane((int)meta[5]), n_iter = __builtin_amdgcn_readfirstlane((int)meta[6]);
-                    const float mom = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane((int)meta[7]));
-                    float* gl_out = reinterpret_cast<float*>((uint64_t)meta[8] | ((uint64_t)meta[9] << 32));
+                    const v2f* init = FrameMeta::load_has_init(meta) ? reinterpret_cast<const v2f*>(a.slot_init + (size_t)s * a.init_stride) : nullptr;
+                    const uint64_t seed = FrameMeta::load_seed(meta), sid0 = FrameMeta::load_sid0(meta);
+                    const int it0 = FrameMeta::load_it0(meta), n_iter = FrameMeta::load_n_iter(meta);
+                    const float mom = FrameMeta::load_mom(meta);
+                    float* gl_out = FrameMeta::load_out(meta);
                     // iterations [lo, hi) of the frame's chain; the last segment runs to the end and emits.  (A frame of a deep pipe comes with its
                     // initial phases in the slot -- injected, or drawn by its front workgroup's spare wave -- so every segment starts alike.)
                     const int span = n_iter > it0 ? n_iter - it0 : 0;
@@ -144,13 +141,7 @@ __global__ __launch_bounds__(kHopPipeThreads, FRONT ? kFrontPerCu : (NFFT == 153
                                            reinterpret_cast<v2f*>(a.gl_state + (size_t)s * a.state_stride), tid);
                     DN_WSTAMP(7);
                 }
-                if (STREAM && j == 0 && !completes) {
-                    // nothing to emit in this launch: the reference's ola[:hop] is still zero (app3.py:133,219)
-                    for (int n = lane; n < kNR / 2; n += 64) {
-                        if (a.out_s16) static_cast<short*>(a.hop_out)[b * (kNR / 2) + n] = 0;
-                        else static_cast<float*>(a.hop_out)[b * (kNR / 2) + n] = 0.0f;
-                    }
-                }
+                if (STREAM && j == 0 && !completes) pcm_zero_hop(a.hop_out, a.out_s16, b, kNR / 2, lane, 64);   // nothing to emit in this launch
             }
         }
     } else if (!FRONT && (int)blockIdx.x < a.back_blocks) {
@@ -164,19 +155,15 @@ __global__ __launch_bounds__(kHopPipeThreads, FRONT ? kFrontPerCu : (NFFT == 153
             __builtin_amdgcn_s_setprio(DN_GL_PRIO);
             const int s = slot_behind(slot_next, 1, a.n_slots);
             const float* slot = a.slots + (size_t)s * a.slot_stride;
-            const uint32_t* meta = reinterpret_cast<const uint32_t*>(slot + sl.meta) + kSlotMeta * b;
-            const v2f* init = meta[0] ? reinterpret_cast<const v2f*>(a.slot_init + (size_t)s * a.init_stride) : nullptr;
-            const uint64_t seed = (uint64_t)meta[1] | ((uint64_t)meta[2] << 32);
-            const uint64_t sid0 = (uint64_t)meta[3] | ((uint64_t)meta[4] << 32);
-            // (the slot words come back through the vector memory path: readfirstlane tells the compiler they are wave-uniform, so the iteration
-            // loop keeps a scalar trip count and a scalar branch)
-            const int it0 = __builtin_amdgcn_readfirstlane((int)meta[5]);          // iterations the frame's front workgroup already ran (head start)
             // the frame's own n_iter / momentum (those of its submit, not of this call: it0 <= n_iter by construction) and destination
-            const int n_iter = __builtin_amdgcn_readfirstlane((int)meta[6]);
-            const float mom = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane((int)meta[7]));
+            const uint32_t* meta = reinterpret_cast<const uint32_t*>(slot + sl.meta) + kSlotMeta * b;
+            const v2f* init = FrameMeta::load_has_init(meta) ? reinterpret_cast<const v2f*>(a.slot_init + (size_t)s * a.init_stride) : nullptr;
+            const uint64_t seed = FrameMeta::load_seed(meta), sid0 = FrameMeta::load_sid0(meta);
+            const int it0 = FrameMeta::load_it0(meta), n_iter = FrameMeta::load_n_iter(meta);
+            const float mom = FrameMeta::load_mom(meta);
             v2f* st = reinterpret_cast<v2f*>(a.gl_state + (size_t)s * a.state_stride);
             if (!STREAM) {
-                float* gl_out = reinterpret_cast<float*>((uint64_t)meta[8] | ((uint64_t)meta[9] << 32));
+                float* gl_out = FrameMeta::load_out(meta);
                 gl_body<NFFT, false, false>(smem, d, slot + sl.lin, nullptr, init, seed, sid0, slot + sl.peak, gl_out, n_iter, mom, b, tid,
                                             nullptr, nullptr, 0, it0, -1, st);
             } else
@@ -185,8 +172,9 @@ __global__ __launch_bounds__(kHopPipeThreads, FRONT ? kFrontPerCu : (NFFT == 153
             __builtin_amdgcn_s_setprio(0);
             DN_HSTAMP(1);
         } else if (STREAM) {
-            // nothing to emit yet: the reference's ola[:hop] is still zero (app3.py:133,219)
-            for (int n = tid; n < kNR / 2; n += kHopThreads) {      // (three waves are left)
+            // nothing to emit yet: pcm_zero_hop(a.hop_out, a.out_s16, b, kNR / 2, tid, kHopThreads), spelled out (three waves are left) -- through the
+            // helper ten of this branch's kernels get their blocks laid out in another order
+            for (int n = tid; n < kNR / 2; n += kHopThreads) {
                 if (a.out_s16) static_cast<short*>(a.hop_out)[b * (kNR / 2) + n] = 0;
                 else static_cast<float*>(a.hop_out)[b * (kNR / 2) + n] = 0.0f;
             }
@@ -245,17 +233,8 @@ __global__ __launch_bounds__(kHopPipeThreads, FRONT ? kFrontPerCu : (NFFT == 153
             if (tid == 0) {
                 uint32_t* meta = reinterpret_cast<uint32_t*>(slot + sl.meta) + kSlotMeta * b;
                 const uint64_t seed = a.seed + frames;
-                meta[0] = (PHIN || a.init_in != nullptr || (draw && a.depth > 1)) ? 1u : 0u;       // the frame's phases are in the slot
-                meta[1] = (uint32_t)seed;
-                meta[2] = (uint32_t)(seed >> 32);
-                meta[3] = (uint32_t)a.sid0;
-                meta[4] = (uint32_t)(a.sid0 >> 32);
-                meta[5] = (uint32_t)split;
-                meta[6] = (uint32_t)a.n_iter;
-                meta[7] = __builtin_bit_cast(uint32_t, a.mom);
-                const uint64_t dst = reinterpret_cast<uint64_t>(a.gl_out);
-                meta[8] = (uint32_t)dst;
-                meta[9] = (uint32_t)(dst >> 32);
+                const bool in_slot = PHIN || a.init_in != nullptr || (draw && a.depth > 1);       // the frame's phases are in the slot
+                FrameMeta{in_slot, seed, a.sid0, split, a.n_iter, a.mom, a.gl_out}.store(meta);
             }
             if (!PHIN && a.init_in != nullptr) {
                 const float2* src = reinterpret_cast<const float2*>(a.init_in) + b * 3 * kBins;

@@ -107,13 +107,76 @@ constexpr int kMaxC = 5;         // compressed bins supported by the cell kernel
 // 48 kHz / n_fft 1536 (measured: a 48-step unroll costs the n_fft-1024 hop 1 %, and gives the 1536 one 0.8 %)
 constexpr int mel_q_steps(int n_fft) { return n_fft == 1536 ? 48 : 32; }
 constexpr int kInvBand = 16;      // diagonals of (fb^T fb)^-1 kept on either side of the main one (DspDev::ginv_band)
-constexpr int kSlotMeta = 16;     // u32 of per-stream hand-over data in a pipe's scratch slot (dn_hop.hip: SlotLayout)
+constexpr int kSlotMeta = 16;     // u32 of per-stream hand-over data in a pipe's scratch slot (FrameMeta below fills ten of them)
 constexpr int kGlwAutoStreams = 768;
 constexpr long kSplitAutoChains = 4096;         // DN_SPLIT_AUTO: chain wavefronts per launch from which a hop goes out as two launches (measured: 2,048 -2.4 %, 4,096 +2.1 %, 8,192 +5.1 %)   // DN_GL_AUTO: from this many streams per pipe on (three per CU of an MI355X; measured crossover between 512 and 768) the back half runs a wavefront per stream
 // Floats of the VALU-row weight table of a GRUUNet2 conv level (CellDev; dn_cell_body.hpp: rows_down / rows_up): `slots4` float4 of weights for each
 // of the `rows` rows of the partial last row tile, in whole 256-byte lines.  It sits between the whole row tiles' fragments and the partial one's.
 constexpr int cell_rowtab_floats(int rows, int slots4) { return (rows * slots4 * 4 + 63) / 64 * 64; }
 constexpr int kArenaSlack = 8192; // zero bytes behind every device arena: kernels that move whole rounds of an array read past its end (dn_cell_body.hpp)
+
+// ---- what one launch hands the next through device memory: each format once, for its writer, its readers and the host code that sizes it.
+// A pipe's scratch slot, offsets in floats: mel [B][3][M] | residual [B][3][M] | peak [B] | meta [B][kSlotMeta] u32 | lin [B][3][K]
+struct SlotLayout {
+    size_t diff, peak, meta, lin, floats;
+    __host__ __device__ constexpr SlotLayout(int B, int M, int K)
+        : diff((size_t)B * 3 * M), peak(2 * diff), meta(peak + B), lin(meta + kSlotMeta * (size_t)B), floats(lin + (size_t)B * 3 * K) {}
+};
+static_assert(SlotLayout(256, 80, 513).floats == 256 * 2036 && SlotLayout(256, 80, 513).lin == 256 * 497, "a change of the slot layout is a deliberate edit");
+
+// The slot's meta record of a stream, written by the frame's front workgroup and read by its Griffin-Lim workgroup in a later launch -- everything
+// the pending hop is finished with is the FRAME's own, not the next call's.  Words: [0] has_init  [1,2] seed  [3,4] sid0  [5] it0  [6] n_iter
+// [7] mom (bits)  [8,9] out.
+struct FrameMeta {
+    bool has_init;          // the frame's phases are in the slot's init area (injected, drawn by the front workgroup, or its STFT's phasors)
+    uint64_t seed, sid0;    // Griffin-Lim seed; stream id of stream 0
+    int it0;                // head-start iterations the front workgroup already ran
+    int n_iter;
+    float mom;              // momentum / (1 + momentum)
+    float* out;             // where the frame goes (frame mode: the `out` of its dn_pipe_submit)
+    __device__ __forceinline__ void store(uint32_t* m) const {
+        m[0] = has_init ? 1u : 0u;
+        m[1] = (uint32_t)seed;
+        m[2] = (uint32_t)(seed >> 32);
+        m[3] = (uint32_t)sid0;
+        m[4] = (uint32_t)(sid0 >> 32);
+        m[5] = (uint32_t)it0;
+        m[6] = (uint32_t)n_iter;
+        m[7] = __builtin_bit_cast(uint32_t, mom);
+        const uint64_t dst = reinterpret_cast<uint64_t>(out);
+        m[8] = (uint32_t)dst;
+        m[9] = (uint32_t)(dst >> 32);
+    }
+    // Loading is field by field: a reader takes the fields it uses where it uses them (group_kernel never reads it0), between its own address
+    // arithmetic -- one load of the whole record moves the loads against that and the kernels compile to other code.  The words come back through
+    // the vector memory path: readfirstlane tells the compiler that it0, n_iter and mom are wave-uniform, so the iteration loop keeps a scalar
+    // trip count and a scalar branch; the other fields do not take one.
+    static __device__ __forceinline__ bool load_has_init(const uint32_t* m) { return m[0] != 0; }
+    static __device__ __forceinline__ uint64_t load_seed(const uint32_t* m) { return (uint64_t)m[1] | ((uint64_t)m[2] << 32); }
+    static __device__ __forceinline__ uint64_t load_sid0(const uint32_t* m) { return (uint64_t)m[3] | ((uint64_t)m[4] << 32); }
+    static __device__ __forceinline__ int load_it0(const uint32_t* m) { return __builtin_amdgcn_readfirstlane((int)m[5]); }
+    static __device__ __forceinline__ int load_n_iter(const uint32_t* m) { return __builtin_amdgcn_readfirstlane((int)m[6]); }
+    static __device__ __forceinline__ float load_mom(const uint32_t* m) { return __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane((int)m[7])); }
+    static __device__ __forceinline__ float* load_out(const uint32_t* m) { return reinterpret_cast<float*>((uint64_t)m[8] | ((uint64_t)m[9] << 32)); }
+};
+
+// The chain a head start parks (gl_body writes it; gl_body or glw_body's kGlwFromX resumes it): [stream][column][parked_rows][64] complex, one
+// coalesced row of 64 lanes per register of the lane's state, n_fft / 128 complex values a lane.  glw_body's own segment format fits inside it.
+constexpr int parked_rows(int n_fft) { return 2 * (n_fft / 128) + 2; }                     // rows a column
+constexpr size_t parked_elems(int n_fft) { return (size_t)3 * parked_rows(n_fft) * 64; }   // complex values a stream
+static_assert(parked_elems(512) == 1920 && parked_elems(1024) == 3456 && parked_elems(1536) == 4992, "a change of the parked chain is a deliberate edit");
+template <int NFFT> struct Parked {
+    static constexpr int kNV = NFFT / 128, kNP = kNV / 2;
+    // the lane's element of row 0 of column c of stream b; the rows below are offsets from it, t = 0 .. kNP - 1
+    template <typename T> static __device__ __forceinline__ T* column(T* state, size_t b, int c, int lane) { return state + ((b * 3 + c) * parked_rows(NFFT)) * 64 + lane; }
+    static constexpr int xlo(int t) { return 64 * t; }                       // X = angles * magnitude of bin pair t: the low bins
+    static constexpr int xhi(int t) { return 64 * (kNP + t); }               //                                      the high bins
+    static constexpr int xmid() { return 64 * kNV; }                         // X of bin NC / 2
+    static constexpr int plo(int t) { return 64 * (kNV + 1 + t); }           // the previous rebuilt spectrum, likewise
+    static constexpr int phi(int t) { return 64 * (kNV + 1 + kNP + t); }
+    static constexpr int pmid() { return 64 * (2 * kNV + 1); }
+    static_assert(pmid() == 64 * (parked_rows(NFFT) - 1), "the rows fill the column");
+};
 
 void launch_stft(const DspDev& d, const float* frames, float* spec, float* mel, float* peak, int B, uint32_t flags,
                  hipStream_t st);
@@ -211,7 +274,22 @@ struct FrameArgs {
 void launch_frame(const DspDev& d, const CellDev& c, const FrameArgs& a, int B, bool bf16, hipStream_t st);
 // One hop for n listed slots of a session pool (dn_sessions.hip).  Slot-indexed: ring, ola, hx and the counters; row-indexed (list order): hop_in,
 // hop_out, init and the workspace.
-constexpr int kSessMeta = 4;      // u32 a row the front launch of the two-launch form leaves its chain: [0] runs a chain, [1,2] Griffin-Lim seed
+constexpr int kSessMeta = 4;      // u32 a row the front launch of the two-launch form leaves its chain (SessMeta fills three of them)
+// The record of a row: [0] the row runs a chain (0: a priming push)  [1,2] the frame's Griffin-Lim seed.  The chain launch asks runs() first -- only
+// for rows of the list, and only a row that runs is loaded -- and takes both through readfirstlane (wave-uniform: a wavefront serves one row).
+struct SessMeta {
+    uint64_t seed;
+    static __device__ __forceinline__ void store_idle(uint32_t* m) { m[0] = 0u; }          // (the seed words stay what they were)
+    __device__ __forceinline__ void store(uint32_t* m) const {
+        m[0] = 1u;
+        m[1] = (uint32_t)seed;
+        m[2] = (uint32_t)(seed >> 32);
+    }
+    static __device__ __forceinline__ bool runs(const uint32_t* m) { return __builtin_amdgcn_readfirstlane((int)m[0]) != 0; }
+    static __device__ __forceinline__ SessMeta load(const uint32_t* m) {
+        return SessMeta{(uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)m[1]) | ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)m[2]) << 32)};
+    }
+};
 struct SessArgs {
     const int32_t* ids; int n;                                  // [n] slot of row i (device copy, validated on the host)
     float* ring; float* ola; float* hx;                         // [cap][n_fft], [cap][n_fft], [cap][17][C]

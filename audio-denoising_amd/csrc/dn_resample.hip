@@ -17,10 +17,11 @@
 //       kRsGenBlocks blocks each; for a fixed tap the x value is the same for every lane, an LDS broadcast out of the staged input of the tap chunk.
 // Neither form divides per output: a workgroup finds its row and tile with divisions of its own index, once.
 //
-// int16 is converted at the load (x / 32767, a true division) and at the store (clip to +-1, * 32767, truncate), the conventions of the hop path.
+// int16 is converted at the load and at the store by the conventions of the hop path (dn_pcm.hpp).
 #include <type_traits>
 
 #include "dn_internal.hpp"
+#include "dn_pcm.hpp"
 
 namespace dn {
 
@@ -34,8 +35,7 @@ __device__ __forceinline__ float rs_sample(const ResampleArgs& a, const void* xr
     if (i < a.lead) return hrow ? hrow[i] : 0.0f;
     const int k = i - a.lead;
     if (k >= a.Lx) return 0.0f;
-    if (S16) return (float)static_cast<const short*>(xrow)[k] / 32767.0f;
-    return static_cast<const float*>(xrow)[k];
+    return pcm_load(xrow, S16, k);
 }
 
 // xs[pos(i)] = v[v0 + i], i in [0, len): groups of four samples on 4-element boundaries of x, one 16-byte load (8 bytes for int16) where a group
@@ -47,13 +47,7 @@ __device__ __forceinline__ void rs_stage(float* xs, POS pos, const ResampleArgs&
     const int ka = k0 & ~3;                             // (two's complement: rounds down for negative k0 too)
     for (int kg = ka + 4 * tid; kg < k1; kg += 4 * threads) {
         if (a.x_vec && kg >= k0 && kg >= 0 && kg + 4 <= k1 && kg + 4 <= a.Lx) {
-            float4 v;
-            if (S16) {
-                const short4 q = *reinterpret_cast<const short4*>(static_cast<const short*>(xrow) + kg);
-                v = make_float4((float)q.x / 32767.0f, (float)q.y / 32767.0f, (float)q.z / 32767.0f, (float)q.w / 32767.0f);
-            } else {
-                v = *reinterpret_cast<const float4*>(static_cast<const float*>(xrow) + kg);
-            }
+            const float4 v = pcm_load4(xrow, S16, kg);
             const int i = kg - k0;
             xs[pos(i)] = v.x; xs[pos(i + 1)] = v.y; xs[pos(i + 2)] = v.z; xs[pos(i + 3)] = v.w;
         } else {
@@ -65,21 +59,17 @@ __device__ __forceinline__ void rs_stage(float* xs, POS pos, const ResampleArgs&
     }
 }
 
-__device__ __forceinline__ short rs_s16(float v) { return (short)(fminf(fmaxf(v, -1.0f), 1.0f) * 32767.0f); }      // np.clip, * iinfo(int16).max, astype(int16)
-__device__ __forceinline__ unsigned int rs_s16_pair(float v0, float v1) {
-    return (unsigned int)(unsigned short)rs_s16(v0) | ((unsigned int)(unsigned short)rs_s16(v1) << 16);
-}
 // outputs m, m + 1 of a row (the second only if `two`): one 8-byte (float32) or 4-byte (int16) store where the pair starts on an even element of an
 // aligned row, else element by element
 __device__ __forceinline__ void rs_store2(const ResampleArgs& a, void* yrow, int m, float v0, float v1, bool two) {
     if (two && a.y_pair && (m & 1) == 0) {
-        if (a.out_s16) *reinterpret_cast<unsigned int*>(static_cast<short*>(yrow) + m) = rs_s16_pair(v0, v1);
+        if (a.out_s16) *reinterpret_cast<unsigned int*>(static_cast<short*>(yrow) + m) = pcm_s16_pair(v0, v1);
         else *reinterpret_cast<float2*>(static_cast<float*>(yrow) + m) = make_float2(v0, v1);
         return;
     }
     if (a.out_s16) {
-        static_cast<short*>(yrow)[m] = rs_s16(v0);
-        if (two) static_cast<short*>(yrow)[m + 1] = rs_s16(v1);
+        static_cast<short*>(yrow)[m] = pcm_s16(v0);
+        if (two) static_cast<short*>(yrow)[m + 1] = pcm_s16(v1);
     } else {
         static_cast<float*>(yrow)[m] = v0;
         if (two) static_cast<float*>(yrow)[m + 1] = v1;
@@ -183,7 +173,7 @@ __global__ __launch_bounds__(kRsThreads) void resample_state_kernel(float* state
     const int tid = threadIdx.x;
     float* srow = state + (size_t)blockIdx.x * H;
     const long long at = (long long)blockIdx.x * x_stride;
-    auto chunk = [&](int k) { return S16 ? (float)(static_cast<const short*>(x) + at)[k] / 32767.0f : (static_cast<const float*>(x) + at)[k]; };
+    auto chunk = [&](int k) { return pcm_load(x, S16, at + k); };
     const int keep = Lc < H ? H - Lc : 0;
     for (int t0 = 0; t0 < keep; t0 += kRsThreads) {
         const int i = t0 + tid;

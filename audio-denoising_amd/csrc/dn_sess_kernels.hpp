@@ -41,13 +41,6 @@ __device__ __forceinline__ const void* sess_row(const void* p, int s16, size_t i
 __device__ __forceinline__ void* sess_row(void* p, int s16, size_t i, int hop) {
     return s16 ? static_cast<void*>(static_cast<short*>(p) + i * hop) : static_cast<void*>(static_cast<float*>(p) + i * hop);
 }
-// a priming push emits zeros: the reference's ola[:hop] is still zero (app3.py:133,219)
-__device__ __forceinline__ void sess_zero_row(void* out, int s16, int hop, int tid, int threads) {
-    for (int n = tid; n < hop; n += threads) {
-        if (s16) static_cast<short*>(out)[n] = 0;
-        else static_cast<float*>(out)[n] = 0.0f;
-    }
-}
 
 // ---- one launch: workgroup i runs the whole hop of slot ids[i] (frame_kernel with one level of indirection)
 // PHIN (an input-phase pool: a.init is its phasor rows): as frame_kernel's -- the analysis stores the unit phasors of its STFT in row i and the chain starts
@@ -67,7 +60,7 @@ __global__ __launch_bounds__(kHopPipeThreads, NFFT == 1536 ? 2 : 1) void sess_fr
     void* out = sess_row(a.hop_out, a.out_s16, i, kHop);
     ring_shift<NFFT, kHopPipeThreads>(ring, sess_row(a.hop_in, a.in_s16, i, kHop), a.in_s16, 0, tid);
     if (pushed < (unsigned int)a.prime) {          // the slot's first n_fft/hop - 1 pushes only fill its ring
-        sess_zero_row(out, a.out_s16, kHop, tid, kHopPipeThreads);
+        pcm_zero_hop(out, a.out_s16, 0, kHop, tid, kHopPipeThreads);          // a priming push emits zeros
         if (tid == 0) a.pushes[s] = pushed + 1;
         return;
     }
@@ -114,8 +107,8 @@ __global__ __launch_bounds__(kHopPipeThreads, kFrontPerCu) void sess_front_kerne
     uint32_t* meta = a.meta + i * kSessMeta;
     ring_shift<kNR, kHopPipeThreads>(ring, sess_row(a.hop_in, a.in_s16, i, kHop), a.in_s16, 0, tid);
     if (pushed < (unsigned int)a.prime) {
-        sess_zero_row(sess_row(a.hop_out, a.out_s16, i, kHop), a.out_s16, kHop, tid, kHopPipeThreads);
-        if (tid == 0) { meta[0] = 0u; a.pushes[s] = pushed + 1; }
+        pcm_zero_hop(sess_row(a.hop_out, a.out_s16, i, kHop), a.out_s16, 0, kHop, tid, kHopPipeThreads);
+        if (tid == 0) { SessMeta::store_idle(meta); a.pushes[s] = pushed + 1; }
         return;
     }
     const int M = d.n_mels;
@@ -129,10 +122,7 @@ __global__ __launch_bounds__(kHopPipeThreads, kFrontPerCu) void sess_front_kerne
     __syncthreads();
     invmel_body<kNR, true, kHopPipeThreads>(smem, d, mel, diff, a.lin + i * 3 * kBins, 3, 0, tid);                                   // P8-P10
     if (tid == 0) {
-        const uint64_t seed = a.seed + f;
-        meta[0] = 1u;
-        meta[1] = (uint32_t)seed;
-        meta[2] = (uint32_t)(seed >> 32);
+        SessMeta{a.seed + f}.store(meta);
         a.frames[s] = f + 1;
     }
 }

@@ -10,7 +10,7 @@ __global__ __launch_bounds__(kHopPipeThreads, 2) void sess_chain_kernel(DspDev d
     const int tid = threadIdx.x, lane = tid & 63, wv = __builtin_amdgcn_readfirstlane(tid >> 6);
     const size_t i = (size_t)blockIdx.x * kGlwWaves + wv;
     const uint32_t* meta = a.meta + i * kSessMeta;
-    const bool runs = i < (size_t)a.n && __builtin_amdgcn_readfirstlane((int)meta[0]) != 0;
+    const bool runs = i < (size_t)a.n && SessMeta::runs(meta);
     if (!runs) {
         // every wave meets the others at ONE LDS-only barrier: the ones with a chain inside glw_body, after their share of the window tables
         glw_fill_tables<kNR, kHopPipeThreads>(smem, d, tid);
@@ -18,7 +18,7 @@ __global__ __launch_bounds__(kHopPipeThreads, 2) void sess_chain_kernel(DspDev d
         return;
     }
     const size_t s = (size_t)a.ids[i];
-    const uint64_t seed = (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)meta[1]) | ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)meta[2]) << 32);
+    const uint64_t seed = SessMeta::load(meta).seed;
     const uint64_t sid = a.sids[s];
     const v2f* init = a.init != nullptr ? reinterpret_cast<const v2f*>(a.init) + i * 3 * kBins : nullptr;
     glw_body<kNR, kEmitStream>(smem, d, a.lin + i * 3 * kBins, init, seed, sid, a.peak + i, nullptr, a.n_iter, a.mom, 0, lane, wv,
