@@ -10,7 +10,7 @@ __version__ = "0.1.0"
 
 def __getattr__(name):
     # ``audio_denoising_amd.SessionPool`` / ``SessionState`` (sessions.py), imported on first use: importing the package stays free of torch
-    if name in ("SessionPool", "SessionState"):
+    if name in ("SessionPool", "SessionState", "RateBank"):
         import importlib
         return getattr(importlib.import_module(__name__ + ".sessions"), name)
     # ``audio_denoising_amd.Denoiser`` (``denoise_clip``: a whole clip per call) / ``DenoiserStream`` (``push`` / ``push_many``), likewise

@@ -35,6 +35,7 @@ SYMBOLS = (
     "dn_server_mag",
     "dn_resample_create", "dn_resample_destroy", "dn_resample_geometry", "dn_resample_get_kernel", "dn_resample_out_len", "dn_resample",
     "dn_resample_state_bytes", "dn_resample_push",
+    "dn_ratebank_create", "dn_ratebank_destroy", "dn_ratebank_geometry", "dn_ratebank_state_stride", "dn_ratebank_ingest", "dn_ratebank_emit",
 )
 
 DN_PEAK_NORMALIZE = 1
@@ -49,6 +50,7 @@ DN_CLIP_GL_PER_COLUMN, DN_CLIP_GL_PER_STREAM = 2, 4
 DN_PHASE_FROM_INPUT = 8
 DN_GLG_WHOLE, DN_GLG_STEPS = 2, 4
 DN_GL_INIT_NORMALIZE = 16
+DN_RATEBANK_IN, DN_RATEBANK_OUT = 0, 1
 ABI_VERSION = 9
 
 
@@ -68,6 +70,11 @@ class DspCfg(C.Structure):
 
 class ResampleCfg(C.Structure):
     _fields_ = [("orig_freq", C.c_int32), ("new_freq", C.c_int32), ("lowpass_filter_width", C.c_int32), ("rolloff", C.c_double)]
+
+
+class RateBankCfg(C.Structure):
+    _fields_ = [("plan_rate", C.c_int32), ("hop", C.c_int32), ("rates", C.c_int32 * 8), ("n_rates", C.c_int32), ("lowpass_filter_width", C.c_int32),
+                ("rolloff", C.c_double)]
 
 
 class DnError(RuntimeError):
@@ -185,6 +192,14 @@ class DnLib:
         L.dn_resample_state_bytes.argtypes = [vp, i32]
         L.dn_resample_state_bytes.restype = C.c_size_t
         L.dn_resample_push.argtypes = [vp, p, p, i32, p, i32, i32, i64, i64, i64, vp]
+        L.dn_ratebank_create.argtypes = [C.POINTER(RateBankCfg), C.POINTER(vp)]
+        L.dn_ratebank_destroy.argtypes = [vp]
+        L.dn_ratebank_destroy.restype = None
+        L.dn_ratebank_geometry.argtypes = [vp, i32] + [C.POINTER(i32)] * 6
+        L.dn_ratebank_state_stride.argtypes = [vp, i32]
+        L.dn_ratebank_state_stride.restype = i32
+        L.dn_ratebank_ingest.argtypes = [vp, p, p, i32, i32, p, p, i32, i64, p, vp]
+        L.dn_ratebank_emit.argtypes = [vp, p, p, i32, i32, p, p, p, i32, i64, vp]
         if L.dn_abi_version() != ABI_VERSION:
             raise ImportError(f"{path}: ABI version {L.dn_abi_version()} != {ABI_VERSION}; rebuild the extension")
 

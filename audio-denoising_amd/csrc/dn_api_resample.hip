@@ -15,23 +15,6 @@ int gcd(int a, int b) {
     return a;
 }
 
-// torchaudio's _get_sinc_resample_kernel with the Hann window, in double, rounded once: [n][KW]
-std::vector<float> hann_table(int o, int n, int width, int lpw, double base) {
-    const int KW = 2 * width + o;
-    const double scale = base / o;
-    std::vector<float> k((size_t)n * KW);
-    for (int p = 0; p < n; ++p)
-        for (int j = 0; j < KW; ++j) {
-            double t = (-(double)p / n + (double)(j - width) / o) * base;
-            t = fmax(-(double)lpw, fmin((double)lpw, t));
-            const double c = cos(t * PI / lpw / 2), window = c * c;
-            t *= PI;
-            const double sinc = t == 0.0 ? 1.0 : sin(t) / t;
-            k[(size_t)p * KW + j] = (float)(sinc * (window * scale));
-        }
-    return k;
-}
-
 int bad_rows(const char* who, const char* what, long long stride, long long need) {
     return fail(DN_ERR_INVALID, std::string(who) + ": " + what + " " + std::to_string(stride) + " is shorter than the " + std::to_string(need) + " samples of a row");
 }
@@ -55,32 +38,60 @@ int check_grid(const char* who, const dn_resampler* r, int32_t B, long long nblk
 
 }  // namespace
 
+// ---- the geometry and the Hann table of a rate pair: shared with the rate banks (dn_api_ratebank.hip)
+int resample_design(const char* who_, int orig, int rate, int lpw, double rolloff, ResampleDesign* out) {
+    const std::string who = who_;
+    if (orig < 1 || rate < 1) return fail(DN_ERR_INVALID, who + ": rates must be positive");
+    if (orig == rate) return fail(DN_ERR_INVALID, who + ": equal rates need no resampler (torchaudio returns the input)");
+    if (lpw < 1) return fail(DN_ERR_INVALID, who + ": lowpass_filter_width must be at least 1");
+    if (!(rolloff > 0.0 && rolloff <= 1.0)) return fail(DN_ERR_INVALID, who + ": rolloff must be in (0, 1]");
+    const int g = gcd(orig, rate), o = orig / g, n = rate / g;
+    const std::string limits = "the kernels take reduced rates o, n <= " + std::to_string(kMaxRate) + " and tables n x taps <= " + std::to_string(kMaxTable) + " floats";
+    if (o > kMaxRate || n > kMaxRate)
+        return fail(DN_ERR_UNSUPPORTED, who + ": " + limits + " (got " + std::to_string(o) + " : " + std::to_string(n) + ")");
+    const double base = (o < n ? o : n) * rolloff;
+    const double w = ceil(lpw * (double)o / base);
+    if (!((2.0 * w + o) * n <= (double)kMaxTable)) {          // (w may be huge, or infinite with a tiny rolloff: the taps are named only where they fit an integer)
+        const double taps = 2.0 * w + o;
+        return fail(DN_ERR_UNSUPPORTED, who + ": " + limits + " (got " + std::to_string(n) + " x " +
+                                            (taps < 1e15 ? std::to_string((long long)taps) : std::string("more than 10^15")) + ")");
+    }
+    out->o = o; out->n = n; out->width = (int)w; out->KW = 2 * out->width + o;
+    out->D = (out->width + o - 1) / o; out->H = out->D * o + out->width;
+    out->base = base;
+    return DN_OK;
+}
+
+// torchaudio's _get_sinc_resample_kernel with the Hann window, in double, rounded once: [n][KW]
+std::vector<float> resample_hann_table(const ResampleDesign& g, int lpw) {
+    const int o = g.o, n = g.n, width = g.width, KW = g.KW;
+    const double base = g.base, scale = base / o;
+    std::vector<float> k((size_t)n * KW);
+    for (int p = 0; p < n; ++p)
+        for (int j = 0; j < KW; ++j) {
+            double t = (-(double)p / n + (double)(j - width) / o) * base;
+            t = fmax(-(double)lpw, fmin((double)lpw, t));
+            const double c = cos(t * PI / lpw / 2), window = c * c;
+            t *= PI;
+            const double sinc = t == 0.0 ? 1.0 : sin(t) / t;
+            k[(size_t)p * KW + j] = (float)(sinc * (window * scale));
+        }
+    return k;
+}
+
 extern "C" {
 
 int dn_resample_create(const dn_resample_cfg* cfg, const float* kernel, dn_resampler** out) {
     if (!cfg || !out) return fail(DN_ERR_INVALID, "dn_resample_create: null argument");
-    if (cfg->orig_freq < 1 || cfg->new_freq < 1) return fail(DN_ERR_INVALID, "dn_resample_create: rates must be positive");
-    if (cfg->orig_freq == cfg->new_freq) return fail(DN_ERR_INVALID, "dn_resample_create: equal rates need no resampler (torchaudio returns the input)");
-    if (cfg->lowpass_filter_width < 1) return fail(DN_ERR_INVALID, "dn_resample_create: lowpass_filter_width must be at least 1");
-    if (!(cfg->rolloff > 0.0 && cfg->rolloff <= 1.0)) return fail(DN_ERR_INVALID, "dn_resample_create: rolloff must be in (0, 1]");
-    const int g = gcd(cfg->orig_freq, cfg->new_freq), o = cfg->orig_freq / g, n = cfg->new_freq / g;
-    const std::string limits = "the kernels take reduced rates o, n <= " + std::to_string(kMaxRate) + " and tables n x taps <= " + std::to_string(kMaxTable) + " floats";
-    if (o > kMaxRate || n > kMaxRate)
-        return fail(DN_ERR_UNSUPPORTED, "dn_resample_create: " + limits + " (got " + std::to_string(o) + " : " + std::to_string(n) + ")");
-    const double base = (o < n ? o : n) * cfg->rolloff;
-    const double w = ceil(cfg->lowpass_filter_width * (double)o / base);
-    if (!((2.0 * w + o) * n <= (double)kMaxTable)) {          // (w may be huge, or infinite with a tiny rolloff: the taps are named only where they fit an integer)
-        const double taps = 2.0 * w + o;
-        return fail(DN_ERR_UNSUPPORTED, "dn_resample_create: " + limits + " (got " + std::to_string(n) + " x " +
-                                            (taps < 1e15 ? std::to_string((long long)taps) : std::string("more than 10^15")) + ")");
-    }
+    ResampleDesign g;
+    DN_TRY(resample_design("dn_resample_create", cfg->orig_freq, cfg->new_freq, cfg->lowpass_filter_width, cfg->rolloff, &g));
     std::unique_ptr<dn_resampler> r(new dn_resampler());
     r->cfg = *cfg;
-    r->o = o; r->n = n; r->width = (int)w; r->KW = 2 * r->width + o;
-    r->D = (r->width + o - 1) / o; r->H = r->D * o + r->width;
+    const int o = g.o, n = g.n;
+    r->o = o; r->n = n; r->width = g.width; r->KW = g.KW; r->D = g.D; r->H = g.H;
     const size_t KW = (size_t)r->KW;
-    r->kernel = kernel ? std::vector<float>(kernel, kernel + (size_t)n * KW) : hann_table(o, n, r->width, cfg->lowpass_filter_width, base);
-    r->small = n <= dn::kRsSmallMaxN && o <= dn::kRsSmallMaxO && (size_t)n * KW <= (size_t)dn::kRsSmallMaxTable;
+    r->kernel = kernel ? std::vector<float>(kernel, kernel + (size_t)n * KW) : resample_hann_table(g, cfg->lowpass_filter_width);
+    r->small = g.small();
     size_t off;
     if (r->small) {
         off = r->arena.add(r->kernel);

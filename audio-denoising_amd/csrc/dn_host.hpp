@@ -244,7 +244,67 @@ struct dn_resampler {
     const float* table = nullptr;
 };
 
+// A page-locked staging ring for small host lists that kernels read straight from host memory: kRing entries of `entry` bytes, entry k handed out
+// again only after the event recorded behind the last launch that read it has completed (the discipline of dn_sessions' id lists).
+struct StageRing {
+    static constexpr int kRing = 4;
+    PinnedBuf<char> host;
+    char* dev = nullptr;                      // the device's view of the entries
+    size_t entry = 0;
+    Event ev[kRing];
+    bool live[kRing] = {};
+    unsigned long long calls = 0;
+    hipError_t create(size_t entry_bytes) {
+        entry = (entry_bytes + 255) & ~size_t(255);
+        hipError_t e = host.alloc(kRing * entry);
+        if (e == hipSuccess) e = host.device_view(&dev);
+        for (int k = 0; k < kRing && e == hipSuccess; ++k) { e = ev[k].create(hipEventDisableTiming); live[k] = false; }
+        return e;
+    }
+    // the next entry, free again: *h to fill on the host, *d what the launch reads
+    hipError_t next(char** h, const char** d) {
+        const int k = (int)(calls % kRing);
+        if (live[k]) { const hipError_t e = hipEventSynchronize(ev[k].get()); if (e != hipSuccess) return e; }
+        *h = host.get() + (size_t)k * entry;
+        *d = dev + (size_t)k * entry;
+        return hipSuccess;
+    }
+    // behind the launch that read the entry next() gave
+    hipError_t staged(hipStream_t st) {
+        const int k = (int)(calls % kRing);
+        const hipError_t e = hipEventRecord(ev[k].get(), st);
+        if (e == hipSuccess) { live[k] = true; ++calls; }
+        return e;
+    }
+    void drain() {                            // the launches that read the ring finish before it goes
+        for (int k = 0; k < kRing; ++k)
+            if (live[k]) (void)hipEventSynchronize(ev[k].get());
+    }
+};
+
+struct dn_ratebank {
+    dn_ratebank_cfg cfg;
+    int n_rates = 0;
+    dn::RateBankRate side[2][dn::kRbMaxRates];     // [0]: down (session rate -> plan, ingest), [1]: up (plan -> session rate, emit)
+    int D[2][dn::kRbMaxRates];                     // delay blocks of each table
+    int stride[2] = {0, 0};                        // floats a slot of each side's state: the largest H, rounded up to 4
+    DevArena arena;                                // every table, [n][KW] each
+    const float* tables = nullptr;
+    StageRing ring;                                // the (slot, rate index) pairs of a call
+    size_t ring_rows = 0;                          // rows an entry holds (grown on demand)
+    std::vector<char> seen;                        // scratch of the duplicate check
+};
+
 // ------------------------------------------------------------------ shared between the units
+// dn_api_resample.hip: the geometry of a rate pair (refusals as dn_resample_create's, under the caller's name) and its Hann table [n][KW]
+struct ResampleDesign {
+    int o, n, width, KW, D, H;
+    double base;
+    bool small() const { return n <= dn::kRsSmallMaxN && o <= dn::kRsSmallMaxO && (size_t)n * KW <= (size_t)dn::kRsSmallMaxTable; }
+};
+int resample_design(const char* who, int orig, int rate, int lpw, double rolloff, ResampleDesign* out);
+std::vector<float> resample_hann_table(const ResampleDesign& g, int lpw);
+
 constexpr uint32_t kHopFlags = DN_CONV_BF16 | DN_PHASE_FROM_INPUT;      // the flag bits of a hop, a pipe and a pool
 
 // dn_api_model.hip: the bias tables of a model for C compressed bins, built and cached on first use

@@ -385,6 +385,31 @@ void launch_resample(const ResampleArgs& a, hipStream_t st);
 // launch that read the old state (stream order)
 void launch_resample_state(float* state, int H, const void* x, int in_s16, long long x_stride, int Lc, int B, hipStream_t st);
 
+// Rate banks (dn_ratebank.hip; dn_ratebank_ingest, dn_ratebank_emit): one side of a bank converts a LIST of rows, row i at the rate of its own
+// session, and updates that session's converter state in the same launch -- one workgroup a row, the small form's chain (dn_resample_body.hpp).
+// A row of rate index r reads [state[slot][:H] | x_i[:chunk_in]] (blocks o samples), writes blocks n outputs, then state[slot][:H] <- the last H
+// samples it read; a row of rate index -1 (the plan's own rate) is a conversion copy of `copy` samples and has no state.
+constexpr int kRbMaxRates = 8;
+constexpr int kRbMaxChunk = 1536;                // samples a row brings at most (48 kHz on a 16 kHz plan of hop 512; 96 kHz on 48 kHz / hop 768)
+constexpr int kRbMaxHist = 80;                   // H at most: the small form's o = 6 : 1 has 79
+constexpr int kRbTile = kRbMaxChunk + kRbMaxHist;
+static_assert(kRbTile >= 1536 + 79, "the tile holds [state | chunk] of the largest accepted rate");
+struct RateBankRate {
+    int o, n, KW, H;                             // the side's reduced pair, taps and history
+    int blocks;                                  // blocks a hop: chunk_in = blocks o samples in, chunk_out = blocks n samples out
+    int table;                                   // offset of its [n][KW] table in `tables`, floats
+};
+struct RateBankArgs {
+    const void* x; int in_s16; long long x_stride;        // [n][x_stride] float32 or int16 (x / 32767)
+    void* y; int out_s16; long long y_stride;             // [n][y_stride] float32 or int16 (clip, * 32767, truncate)
+    float* state; int state_stride;                       // [capacity][state_stride]
+    const int* rows;                                      // [n] x (slot, rate index)
+    const float* tables;
+    int copy;                                             // samples of a plan-rate row
+    RateBankRate r[kRbMaxRates];
+};
+void launch_ratebank(const RateBankArgs& a, int n, hipStream_t st);
+
 }  // namespace dn
 
 // Comparison entry (dn_api_model.hip): the stand-alone fp32 forward on the conv tiles of before the live-row / lane-geometry change.  Not in the

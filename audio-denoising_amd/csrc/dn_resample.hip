@@ -20,61 +20,12 @@
 // int16 is converted at the load and at the store by the conventions of the hop path (dn_pcm.hpp).
 #include <type_traits>
 
-#include "dn_internal.hpp"
-#include "dn_pcm.hpp"
+#include "dn_resample_body.hpp"
 
 namespace dn {
 
-constexpr int kRsTileMax = (kRsTileQ - 1) * kRsSmallMaxO + kRsSmallMaxTable;            // samples of its input tile at most
 constexpr int kRsGenTaps = 128;                                                         // general form: taps staged at a time
 constexpr int kRsGenTile = (kRsGenBlocks - 1) * 1024 + kRsGenTaps;                      // samples of a staged chunk at most (o <= 1024)
-
-// sample i of the row's virtual input (i >= 0): history or zeros, then x, then zeros
-template <bool S16>
-__device__ __forceinline__ float rs_sample(const ResampleArgs& a, const void* xrow, const float* hrow, int i) {
-    if (i < a.lead) return hrow ? hrow[i] : 0.0f;
-    const int k = i - a.lead;
-    if (k >= a.Lx) return 0.0f;
-    return pcm_load(xrow, S16, k);
-}
-
-// xs[pos(i)] = v[v0 + i], i in [0, len): groups of four samples on 4-element boundaries of x, one 16-byte load (8 bytes for int16) where a group
-// lies inside both the tile and the row and the rows are aligned (a.x_vec); sample by sample at the edges, in the history and beyond the row
-template <bool S16, typename POS>
-__device__ __forceinline__ void rs_stage(float* xs, POS pos, const ResampleArgs& a, const void* xrow, const float* hrow, int v0, int len, int tid,
-                                         int threads) {
-    const int k0 = v0 - a.lead, k1 = k0 + len;          // the tile in samples of x (k0 may be negative: history, or the zeros in front)
-    const int ka = k0 & ~3;                             // (two's complement: rounds down for negative k0 too)
-    for (int kg = ka + 4 * tid; kg < k1; kg += 4 * threads) {
-        if (a.x_vec && kg >= k0 && kg >= 0 && kg + 4 <= k1 && kg + 4 <= a.Lx) {
-            const float4 v = pcm_load4(xrow, S16, kg);
-            const int i = kg - k0;
-            xs[pos(i)] = v.x; xs[pos(i + 1)] = v.y; xs[pos(i + 2)] = v.z; xs[pos(i + 3)] = v.w;
-        } else {
-            for (int e = 0; e < 4; ++e) {
-                const int k = kg + e;
-                if (k >= k0 && k < k1) xs[pos(k - k0)] = rs_sample<S16>(a, xrow, hrow, v0 + (k - k0));
-            }
-        }
-    }
-}
-
-// outputs m, m + 1 of a row (the second only if `two`): one 8-byte (float32) or 4-byte (int16) store where the pair starts on an even element of an
-// aligned row, else element by element
-__device__ __forceinline__ void rs_store2(const ResampleArgs& a, void* yrow, int m, float v0, float v1, bool two) {
-    if (two && a.y_pair && (m & 1) == 0) {
-        if (a.out_s16) *reinterpret_cast<unsigned int*>(static_cast<short*>(yrow) + m) = pcm_s16_pair(v0, v1);
-        else *reinterpret_cast<float2*>(static_cast<float*>(yrow) + m) = make_float2(v0, v1);
-        return;
-    }
-    if (a.out_s16) {
-        static_cast<short*>(yrow)[m] = pcm_s16(v0);
-        if (two) static_cast<short*>(yrow)[m + 1] = pcm_s16(v1);
-    } else {
-        static_cast<float*>(yrow)[m] = v0;
-        if (two) static_cast<float*>(yrow)[m + 1] = v1;
-    }
-}
 
 __device__ __forceinline__ const void* rs_xrow(const ResampleArgs& a, int row) {
     const long long at = (long long)row * a.x_stride;
@@ -97,19 +48,14 @@ __global__ __launch_bounds__(kRsThreads) void resample_small_kernel(ResampleArgs
     const int o = a.o, KW = a.KW;
     const void* xrow = rs_xrow(a, row);
     const float* hrow = a.hist ? a.hist + (size_t)row * a.lead : nullptr;
-    auto pos = [](int i) { return SKEW ? i + (i >> 5) : i; };
+    auto pos = [](int i) { return rs_pos<SKEW>(i); };
     for (int i = tid; i < N * KW; i += kRsThreads) ks[i] = a.table[i];
     rs_stage<S16>(xs, pos, a, xrow, hrow, q0 * o, (nq - 1) * o + KW, tid, kRsThreads);
     __syncthreads();
     void* yrow = rs_yrow(a, row);
     for (int ql = tid; ql < nq; ql += kRsThreads) {
         float acc[N];
-        for (int p = 0; p < N; ++p) acc[p] = 0.0f;
-        const int at = ql * o;
-        for (int j = 0; j < KW; ++j) {
-            const float xv = xs[pos(at + j)];
-            for (int p = 0; p < N; ++p) acc[p] = fmaf(ks[p * KW + j], xv, acc[p]);
-        }
+        rs_small_block<N, SKEW>(xs, ks, ql * o, KW, acc);
         const int m = (q0 + ql) * N;          // the block's first output; the last block of a whole signal may be partial
         if (N == 1) {
             if (m < a.Ly) rs_store2(a, yrow, m, acc[0], 0.0f, false);

@@ -662,6 +662,60 @@ size_t dn_resample_state_bytes(const dn_resampler* r, int32_t B);
 int dn_resample_push(const dn_resampler* r, float* state, const void* x, int32_t in_s16, void* y, int32_t out_s16, int32_t B,
                      int64_t blocks, int64_t x_stride, int64_t y_stride, void* stream);
 
+/* ---- Rate banks: the rate adapters of a session pool -------------------------------------------------------------
+ * A pool's tick is a LIST of slots, and its sessions arrive at rates of their own (48 kHz WebRTC, 8 kHz telephony) next to the
+ * plan's.  A bank holds, for every session rate r of a small set, the table r -> plan ("down", o_d : n_d) and the table
+ * plan -> r ("up", o_u : n_u), both dn_resample_create's Hann tables, and converts every listed row at the rate of its own
+ * session in ONE launch a side, updating that session's converter state in the same launch:
+ *   dn_ratebank_ingest   x [n][x_stride] at each row's rate  ->  hop_in [n][hop] float32 at the plan's rate
+ *   dn_ratebank_emit     hop_out [n][hop] float32            ->  y [n][y_stride] at each row's rate
+ * Per hop a session of rate r brings chunk_in = (hop / n_d) o_d samples and receives chunk_out = (hop / o_u) n_u.  A row's samples
+ * equal dn_resample_push with that pair's own dn_resampler fed the session's stream alone, bit for bit (the same chain), and
+ * so does its state row.  Round-trip lag of a session: D_d n_d plan samples (delay_in) plus D_u n_u samples at its rate
+ * (delay_out); the bank does not compensate it.
+ *
+ * Accepted rates -- both directions of r must
+ *   lie inside the small kernel form (n <= 4, o <= 8, n x taps <= 512 floats),
+ *   tile the hop (n_d | hop and o_u | hop),
+ *   bring at least a history per hop (chunk_in >= H_d; the hop itself >= H_u) and fit the staged tile (chunk_in <= 1536).
+ * At a 16 kHz plan (hop 512 or 256) that is 8, 12, 24, 32 and 48 kHz; at 48 kHz / hop 768 it is 12, 16, 24, 32 and 96 kHz.
+ * Anything else (44.1 kHz: 441 : 160 tiles no hop) is DN_ERR_UNSUPPORTED at create, the message names the condition.  A rate
+ * listed twice, equal to the plan's or < 1, n_rates outside [1, 8], hop < 1: DN_ERR_INVALID.
+ *
+ * State: state_in / state_out [dev][capacity][dn_ratebank_state_stride(b, side)] float32, the CALLER's, as dn_resample_push's.
+ * A slot's row holds the H(rate) leading floats of its session; the rest of the row is never read or written.  All zeros is a
+ * fresh session.  Export, import and zeroing on open are plain copies of those rows.
+ * slots / rate_idx [host][n]: the listed slots (each in [0, capacity), none twice) and each one's index into cfg.rates, or -1 for
+ * a session at the plan's own rate, whose row is the conversion copy of hop samples (x / 32767 in, clip * 32767 truncate out) and
+ * has no state.  x_stride / y_stride >= the longest listed chunk; the buffers need hold only (n - 1) stride + the last row's chunk,
+ * and what lies in a row beyond its chunk is neither read nor written.
+ * Every argument is checked on the host before anything is enqueued: a refused call leaves the outputs and the state
+ * untouched.  n == 0 returns DN_OK.  The handle lives on the current HIP device.  It is immutable but for a page-locked staging
+ * ring of the (slot, rate) pairs, so it is NOT thread-safe (one host thread a bank) and NOT capturable into a hipGraph. */
+typedef struct dn_ratebank dn_ratebank;
+typedef struct dn_ratebank_cfg {
+    int32_t plan_rate;
+    int32_t hop;
+    int32_t rates[8];
+    int32_t n_rates;
+    int32_t lowpass_filter_width; /* 6 */
+    double rolloff;               /* 0.99 */
+} dn_ratebank_cfg;
+#define DN_RATEBANK_IN 0
+#define DN_RATEBANK_OUT 1
+int dn_ratebank_create(const dn_ratebank_cfg* cfg, dn_ratebank** out);
+void dn_ratebank_destroy(dn_ratebank* b);
+/* samples per hop in and out, the history of each side (H_d, H_u) and the lags (D_d n_d at the plan's rate, D_u n_u at the
+ * session's); any pointer may be NULL */
+int dn_ratebank_geometry(const dn_ratebank* b, int32_t rate_index, int32_t* chunk_in, int32_t* chunk_out, int32_t* hist_in,
+                         int32_t* hist_out, int32_t* delay_in, int32_t* delay_out);
+/* floats per slot of a side's state: the largest H of that side, rounded up to 4; 0 for a null handle or an unknown side */
+int32_t dn_ratebank_state_stride(const dn_ratebank* b, int32_t side);
+int dn_ratebank_ingest(dn_ratebank* b, const int32_t* slots, const int32_t* rate_idx, int32_t n, int32_t capacity, float* state_in,
+                       const void* x, int32_t in_s16, int64_t x_stride, float* hop_in, void* stream);
+int dn_ratebank_emit(dn_ratebank* b, const int32_t* slots, const int32_t* rate_idx, int32_t n, int32_t capacity, float* state_out,
+                     const float* hop_out, void* y, int32_t out_s16, int64_t y_stride, void* stream);
+
 const char* dn_last_error(void);
 int dn_abi_version(void);
 
