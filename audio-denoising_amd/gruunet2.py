@@ -16,6 +16,7 @@ import torch
 from torch import nn
 
 from . import _lib
+from ._glue import launch
 
 _H = 17  # hidden channels the kernels are built for
 
@@ -159,12 +160,10 @@ class GRUUNet2(nn.Module):
         h0 = hx.detach().contiguous()
         out = torch.empty_like(x)
         h1 = torch.empty_like(h0)
-        with torch.cuda.device(input.device):
-            stream = torch.cuda.current_stream().cuda_stream
-            if self.conv_precision not in ("fp32", "bf16"):
-                raise ValueError("conv_precision must be 'fp32' or 'bf16'")
-            fwd = lib.dn_cell_forward if self.conv_precision == "fp32" else lib.dn_cell_forward_bf16
-            lib.check(fwd(handle, x.data_ptr(), h0.data_ptr(), out.data_ptr(), h1.data_ptr(), B, T, F, Cb, C.c_void_p(stream)))
+        if self.conv_precision not in ("fp32", "bf16"):
+            raise ValueError("conv_precision must be 'fp32' or 'bf16'")
+        fwd = lib.dn_cell_forward if self.conv_precision == "fp32" else lib.dn_cell_forward_bf16
+        launch(lib, input.device, fwd, handle, x.data_ptr(), h0.data_ptr(), out.data_ptr(), h1.data_ptr(), B, T, F, Cb)
         if two_dimmed:
             out = out.squeeze(0)
         return out, h1

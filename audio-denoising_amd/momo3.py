@@ -16,6 +16,7 @@ import torch
 from torch import nn
 
 from . import _lib
+from ._glue import launch
 from .gruunet2 import _Blocks, _ConvBlock, _Holder
 
 
@@ -120,10 +121,8 @@ class MOMO3(nn.Module):
         handle = self._native(input.device)
         x, h0 = input.detach().contiguous(), hx.detach().contiguous()
         out, h1 = torch.empty_like(x), torch.empty_like(h0)
-        with torch.cuda.device(input.device):
-            st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
-            lib.check(lib.dn_momo_forward(handle, x.data_ptr(), h0.data_ptr(), None if p is None else p.data_ptr(), out.data_ptr(), h1.data_ptr(),
-                                          None, B, T, F, Cb, st))
+        launch(lib, input.device, lib.dn_momo_forward, handle, x.data_ptr(), h0.data_ptr(), None if p is None else p.data_ptr(), out.data_ptr(),
+               h1.data_ptr(), None, B, T, F, Cb)
         return (out.squeeze(0) if two_dimmed else out), h1
 
 

@@ -16,6 +16,7 @@ import os
 import torch
 
 from . import _lib
+from ._glue import PCM, check_tensor, launch, pack_phases, ragged_rounds, record_on_stream
 from .gruunet2 import GRUUNet2
 from .transforms import DspPlan, Resample, melscale_fbanks
 
@@ -70,21 +71,18 @@ class Denoiser:
         """zeros(B, 17, C): app3.py:158-165."""
         return torch.zeros(batch, self.model.latent_size, self.num_compressed_bins, dtype=torch.float32, device=self.device)
 
-    def _check(self, t, shape, name, dtype=torch.float32):
-        if not t.is_cuda or t.device != self.device:
-            raise RuntimeError(f"{name} must live on {self.device} (no CPU path)")
-        if t.dtype != dtype or tuple(t.shape) != shape or not t.is_contiguous():
-            raise ValueError(f"{name} must be contiguous {dtype} of shape {shape}; got {t.dtype} {tuple(t.shape)}")
+    def _check(self, t, shape, name, dtypes=(torch.float32,)):
+        check_tensor(t, name, shape, dtypes, self.device, RuntimeError)
 
-    def _angles_ptr(self, init_angles, batch):
-        """(B, K, 3) complex64 as the reference draws it -> [B][3][K] interleaved storage."""
+    def _pack(self, init_angles, *lead):
+        """``pack_phases`` for this denoiser: (*lead, K, 3) complex64 -> [*lead][3][K] interleaved storage; None stays None"""
+        return None if init_angles is None else pack_phases(init_angles, lead, self.n_stft, self.device, self.phase == "input")
+
+    def _angles_ptr(self, init_angles, *lead):
+        """-> (the packed phases, to be kept alive over the launch; their address), (None, None) without ``init_angles``"""
         if init_angles is None:
             return None, None
-        if self.phase == "input":
-            raise ValueError("this denoiser takes its initial phases from the input (phase='input'): init_angles cannot be passed")
-        if tuple(init_angles.shape) != (batch, self.n_stft, 3) or init_angles.dtype != torch.complex64:
-            raise ValueError(f"init_angles must be complex64 of shape {(batch, self.n_stft, 3)}")
-        ia = torch.view_as_real(init_angles.to(self.device).transpose(-1, -2).contiguous())
+        ia = self._pack(init_angles, *lead)
         return ia, ia.data_ptr()
 
     def draw_phases(self, batch: int, seed: int, stream_id0: int = 0) -> torch.Tensor:
@@ -92,9 +90,7 @@ class Denoiser:
         (dn_griffinlim_draw_phases): complex64 (B, n_fft/2+1, 3), real and imaginary part ~ U[0,1) as the reference's
         ``GriffinLim(rand_init=True)`` (app3.py:149-153).  Passing it back as ``init_angles`` reproduces the seeded call bit for bit."""
         buf = torch.empty(batch, 3, self.n_stft, 2, dtype=torch.float32, device=self.device)
-        with torch.cuda.device(self.device):
-            st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
-            self.lib.check(self.lib.dn_griffinlim_draw_phases(self.plan.handle, seed, stream_id0, buf.data_ptr(), batch, st))
+        launch(self.lib, self.device, self.lib.dn_griffinlim_draw_phases, self.plan.handle, seed, stream_id0, buf.data_ptr(), batch)
         return torch.view_as_complex(buf).transpose(-1, -2)
 
     def input_phases(self, frames: torch.Tensor) -> torch.Tensor:
@@ -104,10 +100,8 @@ class Denoiser:
         B = frames.shape[0]
         self._check(frames, (B, self.n_fft), "frames")
         buf = torch.empty(B, 3, self.n_stft, 2, dtype=torch.float32, device=self.device)
-        with torch.cuda.device(self.device):
-            st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
-            self.lib.check(self.lib.dn_stft_phasors(self.plan.handle, frames.data_ptr(), buf.data_ptr(), B,
-                                                    _lib.DN_PEAK_NORMALIZE | _lib.DN_PRE_WINDOW, st))
+        launch(self.lib, self.device, self.lib.dn_stft_phasors, self.plan.handle, frames.data_ptr(), buf.data_ptr(), B,
+               _lib.DN_PEAK_NORMALIZE | _lib.DN_PRE_WINDOW)
         return torch.view_as_complex(buf).transpose(-1, -2)
 
     # -- the hop body
@@ -126,12 +120,9 @@ class Denoiser:
         if seed is None:
             seed = int(torch.randint(0, 2 ** 62, (1,)).item()) if init_angles is None else 0
         ws = self._workspace(B)
-        model_h = self.model._native(self.device)
-        with torch.cuda.device(self.device):
-            st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
-            self.lib.check(self.lib.dn_process_frame(model_h, self.plan.handle, frames.data_ptr(), hx_new.data_ptr(), out.data_ptr(),
-                                                     None if resid is None else resid.data_ptr(), ia_ptr, seed, stream_id0,
-                                                     self.n_iter, self.momentum, ws.data_ptr(), B, self._flags(), st))
+        launch(self.lib, self.device, self.lib.dn_process_frame, self.model._native(self.device), self.plan.handle, frames.data_ptr(),
+               hx_new.data_ptr(), out.data_ptr(), None if resid is None else resid.data_ptr(), ia_ptr, seed, stream_id0, self.n_iter,
+               self.momentum, ws.data_ptr(), B, self._flags())
         return (out, hx_new, resid) if return_residual else (out, hx_new)
 
     # -- clip mode: N hops per call
@@ -146,14 +137,16 @@ class Denoiser:
         """hops n0 .. n0 + n of a sequence of (B, K, 3) complex64 -> [B][n][3][K] interleaved storage."""
         if per_hop is None:
             return None
-        if self.phase == "input":
-            raise ValueError("this denoiser takes its initial phases from the input (phase='input'): init_angles cannot be passed")
         hops = [per_hop[n0 + i] for i in range(n)]
-        for ia in hops:
-            if tuple(ia.shape) != (batch, self.n_stft, 3) or ia.dtype != torch.complex64:
-                raise ValueError(f"init_angles must be complex64 of shape {(batch, self.n_stft, 3)} per hop")
-        z = torch.stack([ia.to(self.device) for ia in hops], dim=1)          # (B, n, K, 3)
-        return torch.view_as_real(z.transpose(-1, -2).contiguous())
+        if any(ia.shape != hops[0].shape or ia.dtype != hops[0].dtype for ia in hops):
+            raise ValueError("init_angles: every hop's phases must have one shape and dtype")
+        return self._pack(torch.stack([ia.to(self.device) for ia in hops], dim=1), batch, n)
+
+    def _clip_workspace(self, need: int) -> torch.Tensor:
+        """the scratch of the clip calls, grown to ``need`` bytes"""
+        if self._clip_ws is None or self._clip_ws.numel() < need:
+            self._clip_ws = torch.empty(need, dtype=torch.uint8, device=self.device)
+        return self._clip_ws
 
     def _clip(self, hops_in: torch.Tensor, ring: torch.Tensor, ola: torch.Tensor, hx: torch.Tensor, init_angles_per_hop, seed: int,
               stream_id0: int, frame_cap: int | None = None, gl: int = 0) -> torch.Tensor:
@@ -167,23 +160,18 @@ class Denoiser:
         s16 = hops_in.dtype == torch.int16
         out = torch.empty_like(hops_in)
         model_h = self.model._native(self.device)
-        with torch.cuda.device(self.device):
-            st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
-            for n0 in range(0, n_hops, per_call):
-                n = min(per_call, n_hops - n0)
-                whole = n == n_hops
-                tin = hops_in if whole else hops_in[:, n0 * self.hop:(n0 + n) * self.hop].contiguous()
-                tout = out if whole else torch.empty_like(tin)
-                ia = self._pack_clip_angles(init_angles_per_hop, B, n0, n)
-                need = self.lib.dn_clip_workspace_bytes_ex(self.plan.handle, B, n, self._flags())
-                if self._clip_ws is None or self._clip_ws.numel() < need:
-                    self._clip_ws = torch.empty(need, dtype=torch.uint8, device=self.device)
-                self.lib.check(self.lib.dn_clip_process(model_h, self.plan.handle, tin.data_ptr(), int(s16), ring.data_ptr(), ola.data_ptr(),
-                                                        hx.data_ptr(), tout.data_ptr(), int(s16), None if ia is None else ia.data_ptr(),
-                                                        seed + n0, stream_id0, self.n_iter, self.momentum, self._clip_ws.data_ptr(), B, n,
-                                                        self._flags() | gl, st))
-                if not whole:
-                    out[:, n0 * self.hop:(n0 + n) * self.hop] = tout
+        for n0 in range(0, n_hops, per_call):
+            n = min(per_call, n_hops - n0)
+            whole = n == n_hops
+            tin = hops_in if whole else hops_in[:, n0 * self.hop:(n0 + n) * self.hop].contiguous()
+            tout = out if whole else torch.empty_like(tin)
+            ia = self._pack_clip_angles(init_angles_per_hop, B, n0, n)
+            ws = self._clip_workspace(self.lib.dn_clip_workspace_bytes_ex(self.plan.handle, B, n, self._flags()))
+            launch(self.lib, self.device, self.lib.dn_clip_process, model_h, self.plan.handle, tin.data_ptr(), int(s16), ring.data_ptr(),
+                   ola.data_ptr(), hx.data_ptr(), tout.data_ptr(), int(s16), None if ia is None else ia.data_ptr(), seed + n0, stream_id0,
+                   self.n_iter, self.momentum, ws.data_ptr(), B, n, self._flags() | gl)
+            if not whole:
+                out[:, n0 * self.hop:(n0 + n) * self.hop] = tout
         return out
 
     def resamplers(self, sample_rate: int):
@@ -197,6 +185,11 @@ class Denoiser:
             pair = self._resamplers[rate] = (Resample(rate, self.sample_rate), Resample(self.sample_rate, rate))
         return pair
 
+    def _prime_ring(self, ring: torch.Tensor, first: torch.Tensor) -> None:
+        """the priming hop of a fresh stream: ``first`` (.., hop) float32 or int16 PCM into the back of its ``ring`` (.., n_fft)"""
+        # (int16 -> float32 as the kernels do it: a true division, by a tensor -- a Python scalar would become a multiplication by its reciprocal)
+        ring[..., self.hop:] = first.float() / torch.tensor(32767.0, device=self.device) if first.dtype == torch.int16 else first
+
     def denoise_clip(self, wave: torch.Tensor, seed: int = 0, stream_id0: int = 0, init_angles=None, frame_cap: int | None = None,
                      sample_rate: int | None = None) -> torch.Tensor:
         """Offline: ``wave`` (B, L) float32 or int16 PCM on the device -> the denoised clips, same shape and dtype, output sample n lined up with
@@ -209,8 +202,7 @@ class Denoiser:
         are resampled to the plan's rate on the device (``transforms.Resample``), denoised by exactly the path above, resampled back and trimmed
         to L samples -- bit for bit that composition, in the dtype of the input; the filters are symmetric, so output sample n still lines up
         with input sample n.  ``init_angles`` then counts the hops of the resampled clip.  ``None`` (or the plan's rate): exactly the call above."""
-        if wave.dim() != 2 or wave.device != self.device or wave.dtype not in (torch.float32, torch.int16):
-            raise ValueError(f"wave must be float32 or int16 (B, L) on {self.device}")
+        check_tensor(wave, "wave", (None, None), PCM, self.device, contiguous=False)
         B, L = wave.shape
         if B == 0 or L == 0:
             return torch.empty_like(wave)
@@ -223,9 +215,7 @@ class Denoiser:
         padded = torch.zeros(B, (n_hops + 1) * self.hop, dtype=wave.dtype, device=self.device)
         padded[:, :L] = wave
         ring = torch.zeros(B, self.n_fft, dtype=torch.float32, device=self.device)
-        first = padded[:, :self.hop]
-        # (int16 -> float32 as the kernels do it: a true division, by a tensor -- a Python scalar would become a multiplication by its reciprocal)
-        ring[:, self.hop:] = first.float() / torch.tensor(32767.0, device=self.device) if wave.dtype == torch.int16 else first
+        self._prime_ring(ring, padded[:, :self.hop])
         ola = torch.zeros_like(ring)
         out = self._clip(padded[:, self.hop:].contiguous(), ring, ola, self.init_hx(B), init_angles, seed, stream_id0, frame_cap)
         return out[:, self.hop:self.hop + L].contiguous()
@@ -233,18 +223,12 @@ class Denoiser:
     # -- clip mode, ragged: every stream its own number of hops
     def _clip_ragged_call(self, tin, n, f0, ring, ola, hx, tout, ia, seed, stream_id0, gl):
         """one dn_clip_process_ragged call: stream b runs ``n[b]`` hops of the packed ``tin`` from hop ``f0[b]`` of its seed sequence on"""
-        B, F = len(n), sum(n)
-        need = self.lib.dn_clip_ragged_workspace_bytes(self.plan.handle, B, F, self._flags())
-        if self._clip_ws is None or self._clip_ws.numel() < need:
-            self._clip_ws = torch.empty(need, dtype=torch.uint8, device=self.device)
-        s16 = tin.dtype == torch.int16
-        model_h = self.model._native(self.device)
-        with torch.cuda.device(self.device):
-            st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
-            self.lib.check(self.lib.dn_clip_process_ragged(model_h, self.plan.handle, tin.data_ptr(), int(s16), ring.data_ptr(), ola.data_ptr(), hx.data_ptr(),
-                                                           tout.data_ptr(), int(s16), None if ia is None else ia.data_ptr(), seed, stream_id0,
-                                                           (C.c_int32 * B)(*n), (C.c_uint64 * B)(*[v & (2 ** 64 - 1) for v in f0]), self.n_iter,
-                                                           self.momentum, self._clip_ws.data_ptr(), B, self._flags() | gl, st))
+        B, s16 = len(n), int(tin.dtype == torch.int16)
+        ws = self._clip_workspace(self.lib.dn_clip_ragged_workspace_bytes(self.plan.handle, B, sum(n), self._flags()))
+        launch(self.lib, self.device, self.lib.dn_clip_process_ragged, self.model._native(self.device), self.plan.handle, tin.data_ptr(), s16,
+               ring.data_ptr(), ola.data_ptr(), hx.data_ptr(), tout.data_ptr(), s16, None if ia is None else ia.data_ptr(), seed, stream_id0,
+               (C.c_int32 * B)(*n), (C.c_uint64 * B)(*[v & (2 ** 64 - 1) for v in f0]), self.n_iter, self.momentum, ws.data_ptr(), B,
+               self._flags() | gl)
 
     def clip_ragged(self, hops_in: torch.Tensor, n_hops, ring: torch.Tensor, ola: torch.Tensor, hx: torch.Tensor, frame0=None, seed: int = 0,
                     stream_id0: int = 0, init_angles: torch.Tensor | None = None, frame_cap: int | None = None, gl: int = 0) -> torch.Tensor:
@@ -253,8 +237,8 @@ class Denoiser:
         ``n_hops[b]`` ``dn_stream_step`` calls on row b of ``ring``, ``ola`` (B, n_fft) and ``hx`` (B, 17, C), advanced in place; hop i of stream b
         draws from ``(seed + frame0[b] + i, stream_id0 + b)`` (``frame0``: B ints, default zeros) or takes ``init_angles[off[b] + i]`` of the
         packed (F, K, 3) complex64.  Returns the packed hops out, in the dtype of ``hops_in``.  At most ``frame_cap`` frames go into one call
-        (default ``CLIP_FRAME_CAP``): in rounds, every stream with hops left runs an equal share of the cap (at most what it has left; streams
-        beyond the cap wait with 0 hops), its ``frame0`` moved on by what it has run."""
+        (default ``CLIP_FRAME_CAP``): in rounds (``ragged_rounds``), every stream with hops left runs an equal share of the cap (at most what it
+        has left; streams beyond the cap wait with 0 hops), its ``frame0`` moved on by what it has run."""
         n_hops = [int(v) for v in n_hops]
         B, F = len(n_hops), sum(n_hops)
         frame0 = [0] * B if frame0 is None else [int(v) for v in frame0]
@@ -263,46 +247,28 @@ class Denoiser:
             raise ValueError("the frame cap must be positive")
         if B < 1 or len(frame0) != B or min(n_hops) < 0:
             raise ValueError("n_hops: one entry >= 0 per stream, at least one stream; frame0: one entry per stream")
-        if hops_in.dim() != 1 or hops_in.dtype not in (torch.float32, torch.int16) or hops_in.numel() != F * self.hop or not hops_in.is_contiguous():
-            raise ValueError(f"hops_in must be contiguous float32 or int16 of shape ({F * self.hop},): sum(n_hops) hops, packed")
-        if hops_in.device != self.device:
-            raise RuntimeError(f"hops_in must live on {self.device} (no CPU path)")
+        check_tensor(hops_in, "hops_in (sum(n_hops) hops, packed)", (F * self.hop,), PCM, self.device, RuntimeError)
         self._check(ring, (B, self.n_fft), "ring")
         self._check(ola, (B, self.n_fft), "ola")
         self._check(hx, (B, self.model.latent_size, self.num_compressed_bins), "hx")
-        ia = None
-        if init_angles is not None:
-            if self.phase == "input":
-                raise ValueError("this denoiser takes its initial phases from the input (phase='input'): init_angles cannot be passed")
-            if tuple(init_angles.shape) != (F, self.n_stft, 3) or init_angles.dtype != torch.complex64:
-                raise ValueError(f"init_angles must be complex64 of shape {(F, self.n_stft, 3)}")
-            ia = torch.view_as_real(init_angles.to(self.device).transpose(-1, -2).contiguous())          # [F][3][K] interleaved
+        ia = self._pack(init_angles, F)
         out = torch.empty_like(hops_in)
-        if F == 0:
-            return out
-        if F <= cap:
-            self._clip_ragged_call(hops_in, n_hops, frame0, ring, ola, hx, out, ia, seed, stream_id0, gl)
-            return out
         off = [0] * (B + 1)
         for b in range(B):
             off[b + 1] = off[b] + n_hops[b]
         done = [0] * B
-        while True:
-            live = [b for b in range(B) if done[b] < n_hops[b]][:cap]
-            if not live:
-                return out
-            q = cap // len(live)
-            n = [0] * B
-            for b in live:
-                n[b] = min(n_hops[b] - done[b], q)
-            rows = torch.cat([torch.arange(off[b] + done[b], off[b] + done[b] + n[b]) for b in live]).to(self.device)          # the round's frames
+        for n in ragged_rounds(n_hops, cap):
+            if sum(n) == F:          # everything fits into one call: the packed tensors as they are
+                self._clip_ragged_call(hops_in, n, frame0, ring, ola, hx, out, ia, seed, stream_id0, gl)
+                break
+            rows = torch.cat([torch.arange(off[b] + done[b], off[b] + done[b] + n[b]) for b in range(B) if n[b]]).to(self.device)   # the round's frames
             tin = hops_in.view(F, self.hop)[rows].reshape(-1)
             tout = torch.empty_like(tin)
             self._clip_ragged_call(tin, n, [frame0[b] + done[b] for b in range(B)], ring, ola, hx, tout, None if ia is None else ia[rows].contiguous(),
                                    seed, stream_id0, gl)
             out.view(F, self.hop)[rows] = tout.view(-1, self.hop)
-            for b in live:
-                done[b] += n[b]
+            done = [done[b] + n[b] for b in range(B)]
+        return out
 
     def _resample_group(self, waves, resample: Resample):
         """1-D clips of one dtype through ``resample`` in ONE call, as zero-padded rows: the zeros behind a row add k * 0 terms to the row's own
@@ -341,8 +307,7 @@ class Denoiser:
         waves = list(waves)
         B = len(waves)
         for w in waves:
-            if w.dim() != 1 or w.device != self.device or w.dtype not in (torch.float32, torch.int16):
-                raise ValueError(f"waves must be 1-D float32 or int16 tensors on {self.device}")
+            check_tensor(w, "waves: each clip", (None,), PCM, self.device, contiguous=False)
         if sample_rates is not None:
             rates = [int(r) for r in sample_rates] if hasattr(sample_rates, "__len__") else [int(sample_rates)] * B
             if len(rates) != B:
@@ -350,18 +315,15 @@ class Denoiser:
             if any(r != self.sample_rate for r in rates):
                 at_plan = self._resample_clips(waves, rates, True)
                 return self._resample_clips(self.denoise_clips(at_plan, seed, stream_id0, init_angles, frame_cap), rates, False, [w.numel() for w in waves])
-        if init_angles is not None:
-            if self.phase == "input":
-                raise ValueError("this denoiser takes its initial phases from the input (phase='input'): init_angles cannot be passed")
-            if len(init_angles) != B:
-                raise ValueError("init_angles: one sequence of phases per clip")
+        if init_angles is not None and len(init_angles) != B:
+            raise ValueError("init_angles: one sequence of phases per clip")
         n_hops = [self.clip_hops(w.numel()) if w.numel() else 0 for w in waves]
         outs = [torch.empty_like(w) for w in waves]
         if B == 0 or sum(n_hops) == 0:
             return outs
         ring = torch.zeros(B, self.n_fft, dtype=torch.float32, device=self.device)
         ola, hx = torch.zeros_like(ring), self.init_hx(B)
-        for dtype in (torch.float32, torch.int16):          # the packed hops of a call have one sample format: the other format's clips wait with 0 hops
+        for dtype in PCM:        # the packed hops of a call have one sample format: the other format's clips wait with 0 hops
             n = [n_hops[b] if waves[b].dtype == dtype else 0 for b in range(B)]
             F = sum(n)
             if F == 0:
@@ -375,8 +337,7 @@ class Denoiser:
                 head = min(L, self.hop)          # the priming hop goes into the ring, the rest is the stream's hops, zero-padded
                 first = torch.zeros(self.hop, dtype=dtype, device=self.device)
                 first[:head] = w[:head]
-                # (int16 -> float32 as the kernels do it: a true division, by a tensor -- a Python scalar would become a multiplication by its reciprocal)
-                ring[b, self.hop:] = first.float() / torch.tensor(32767.0, device=self.device) if dtype == torch.int16 else first
+                self._prime_ring(ring[b], first)
                 packed[at * self.hop:at * self.hop + L - head] = w[head:]
                 if init_angles is not None:
                     if len(init_angles[b]) != n[b]:
@@ -396,11 +357,8 @@ class Denoiser:
         the denoised frames are written to ``out``; initial phases come from the device generator."""
         B = frames.shape[0]
         ws = self._workspace(B)
-        model_h = self.model._native(self.device)
-        with torch.cuda.device(self.device):          # the launch goes to the CURRENT device: make it the denoiser's
-            st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
-            self.lib.check(self.lib.dn_process_frame(model_h, self.plan.handle, frames.data_ptr(), hx.data_ptr(), out.data_ptr(), None, None,
-                                                     seed, stream_id0, self.n_iter, self.momentum, ws.data_ptr(), B, self._flags(), st))
+        launch(self.lib, self.device, self.lib.dn_process_frame, self.model._native(self.device), self.plan.handle, frames.data_ptr(), hx.data_ptr(),
+               out.data_ptr(), None, None, seed, stream_id0, self.n_iter, self.momentum, ws.data_ptr(), B, self._flags())
 
 
 class ServerDenoiser:
@@ -451,23 +409,21 @@ class ServerDenoiser:
         hx1 = torch.empty_like(hx0)
         wave = torch.empty(B, self.hop * (T - 1), dtype=torch.float32, device=dev)
         model_h = self.model._native(dev)
-        with torch.cuda.device(dev):
-            st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
-            lib.check(lib.dn_stft_general(plan.handle, x.data_ptr(), spec.data_ptr(), logmel.data_ptr(), B, L, st))
-            lib.check(lib.dn_cell_forward_ex(model_h, logmel.data_ptr(), hx0.data_ptr(), out.data_ptr(), hx1.data_ptr(), B, T, self.n_mels, Cb,
-                                             self.hx_decay, st))
-            if self.n_iter is not None:
-                mag = torch.empty(B, T, self.n_stft, dtype=torch.float32, device=dev)
-                ws = torch.empty(max(1, int(lib.dn_griffinlim_general_workspace_bytes(plan.handle, B, T))), dtype=torch.uint8, device=dev)
-                lib.check(lib.dn_server_mag(plan.handle, logmel.data_ptr(), out.data_ptr(), mag.data_ptr(), B * T, st))
-                from_input = self.phase == "input"
-                lib.check(lib.dn_griffinlim_general(plan.handle, mag.data_ptr(), spec.data_ptr() if from_input else None, self.seed + self.requests, 0,
-                                                    wave.data_ptr(), ws.data_ptr(), B, T, self.n_iter, self.momentum,
-                                                    _lib.DN_GL_INIT_NORMALIZE if from_input else 0, st))
-                self.requests += 1
-                return wave, hx1
-            lib.check(lib.dn_server_rows(plan.handle, logmel.data_ptr(), out.data_ptr(), spec.data_ptr(), spec.data_ptr(), B * T, st))
-            lib.check(lib.dn_istft_general(plan.handle, spec.data_ptr(), wave.data_ptr(), B, T, st))
+        launch(lib, dev, lib.dn_stft_general, plan.handle, x.data_ptr(), spec.data_ptr(), logmel.data_ptr(), B, L)
+        launch(lib, dev, lib.dn_cell_forward_ex, model_h, logmel.data_ptr(), hx0.data_ptr(), out.data_ptr(), hx1.data_ptr(), B, T, self.n_mels, Cb,
+               self.hx_decay)
+        if self.n_iter is not None:
+            mag = torch.empty(B, T, self.n_stft, dtype=torch.float32, device=dev)
+            ws = torch.empty(max(1, int(lib.dn_griffinlim_general_workspace_bytes(plan.handle, B, T))), dtype=torch.uint8, device=dev)
+            launch(lib, dev, lib.dn_server_mag, plan.handle, logmel.data_ptr(), out.data_ptr(), mag.data_ptr(), B * T)
+            from_input = self.phase == "input"
+            launch(lib, dev, lib.dn_griffinlim_general, plan.handle, mag.data_ptr(), spec.data_ptr() if from_input else None,
+                   self.seed + self.requests, 0, wave.data_ptr(), ws.data_ptr(), B, T, self.n_iter, self.momentum,
+                   _lib.DN_GL_INIT_NORMALIZE if from_input else 0)
+            self.requests += 1
+            return wave, hx1
+        launch(lib, dev, lib.dn_server_rows, plan.handle, logmel.data_ptr(), out.data_ptr(), spec.data_ptr(), spec.data_ptr(), B * T)
+        launch(lib, dev, lib.dn_istft_general, plan.handle, spec.data_ptr(), wave.data_ptr(), B, T)
         return wave, hx1
 
 
@@ -546,9 +502,7 @@ class _Pipe:
     def counters(self):
         """(pushes, frames, pending) of the device-resident control block.  Synchronises the current stream."""
         a, b, c = C.c_uint64(), C.c_uint64(), C.c_int32()
-        with torch.cuda.device(self.dn.device):
-            st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
-            self.lib.check(self.lib.dn_pipe_get_counters(self.handle, C.byref(a), C.byref(b), C.byref(c), st))
+        launch(self.lib, self.dn.device, self.lib.dn_pipe_get_counters, self.handle, C.byref(a), C.byref(b), C.byref(c))
         return a.value, b.value, bool(c.value)
 
 
@@ -570,12 +524,10 @@ class HopPipeline(_Pipe):
         if check_weights:
             self._bind()
         keep, ia_ptr = d._angles_ptr(init_angles, self.batch)
-        with torch.cuda.device(d.device):
-            st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
-            self.lib.check(self.lib.dn_pipe_submit(self.handle, frames.data_ptr(), hx.data_ptr(), out.data_ptr(), ia_ptr, seed, stream_id0,
-                                                   d.n_iter, d.momentum, st))
-            if keep is not None and not torch.cuda.is_current_stream_capturing():
-                keep.record_stream(torch.cuda.current_stream())     # the launch copies the phases into its scratch slot
+        launch(self.lib, d.device, self.lib.dn_pipe_submit, self.handle, frames.data_ptr(), hx.data_ptr(), out.data_ptr(), ia_ptr, seed, stream_id0,
+               d.n_iter, d.momentum)
+        if keep is not None:
+            record_on_stream(keep, d.device)     # the launch copies the phases into its scratch slot
 
     def submit_group(self, frames: torch.Tensor, hx: torch.Tensor, out: torch.Tensor, seed: int = 0, stream_id0: int = 0,
                      init_angles: torch.Tensor | None = None, check_weights: bool = True) -> None:
@@ -591,27 +543,15 @@ class HopPipeline(_Pipe):
         H = frames.shape[0]
         if check_weights:
             self._bind()
-        ia_ptr, ia_stride, keep = None, 0, []
-        if init_angles is not None:
-            if init_angles.shape[0] != H:
-                raise ValueError("init_angles: one set of phases per hop of the group")
-            keep = [d._angles_ptr(init_angles[h], self.batch)[0] for h in range(H)]
-            packed = torch.stack(keep)                    # (H, B, 3, K, 2) float32, contiguous
-            keep = [packed]
-            ia_ptr, ia_stride = packed.data_ptr(), packed.stride(0)
-        with torch.cuda.device(d.device):
-            cur = torch.cuda.current_stream()
-            self.lib.check(self.lib.dn_pipe_submit_group(self.handle, frames.data_ptr(), frames.stride(0) if H > 1 else 0, hx.data_ptr(), out.data_ptr(),
-                                                         out.stride(0) if H > 1 else 0, ia_ptr, ia_stride, seed, stream_id0, H, d.n_iter, d.momentum,
-                                                         C.c_void_p(cur.cuda_stream)))
-            for k in keep:
-                if not torch.cuda.is_current_stream_capturing():
-                    k.record_stream(cur)
+        keep, ia_ptr = d._angles_ptr(init_angles, H, self.batch)          # (H, B, 3, K, 2) float32, contiguous
+        launch(self.lib, d.device, self.lib.dn_pipe_submit_group, self.handle, frames.data_ptr(), frames.stride(0) if H > 1 else 0, hx.data_ptr(),
+               out.data_ptr(), out.stride(0) if H > 1 else 0, ia_ptr, 0 if keep is None else keep.stride(0), seed, stream_id0, H, d.n_iter,
+               d.momentum)
+        if keep is not None:
+            record_on_stream(keep, d.device)
 
     def flush(self) -> None:
-        with torch.cuda.device(self.dn.device):
-            st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
-            self.lib.check(self.lib.dn_pipe_flush(self.handle, self.dn.n_iter, self.dn.momentum, st))
+        launch(self.lib, self.dn.device, self.lib.dn_pipe_flush, self.handle, self.dn.n_iter, self.dn.momentum)
 
 
 class PipelinedStream(_Pipe):
@@ -633,20 +573,16 @@ class PipelinedStream(_Pipe):
     def push_(self, hop: torch.Tensor, out: torch.Tensor, init_angles: torch.Tensor | None = None, check_weights: bool = True) -> None:
         """Allocation-free push: ``out`` (same shape/dtype family as ``hop``) receives the emitted samples."""
         d = self.dn
-        for t, name in ((hop, "hop"), (out, "out")):
-            if t.device != d.device or tuple(t.shape) != (self.batch, d.hop) or t.dtype not in (torch.float32, torch.int16) \
-                    or not t.is_contiguous():
-                raise ValueError(f"{name} must be contiguous float32 or int16 of shape {(self.batch, d.hop)} on {d.device}")
+        shape = (self.batch, d.hop)
+        check_tensor(hop, "hop", shape, PCM, d.device)
+        check_tensor(out, "out", shape, PCM, d.device)
         if check_weights:
             self._bind()
         keep, ia_ptr = d._angles_ptr(init_angles, self.batch)
-        with torch.cuda.device(d.device):
-            cur = torch.cuda.current_stream()
-            self.lib.check(self.lib.dn_pipe_stream_push(self.handle, hop.data_ptr(), int(hop.dtype == torch.int16), out.data_ptr(),
-                                                        int(out.dtype == torch.int16), ia_ptr, self.seed, self.stream_id0, d.n_iter,
-                                                        d.momentum, C.c_void_p(cur.cuda_stream)))
-            if keep is not None and not torch.cuda.is_current_stream_capturing():
-                keep.record_stream(cur)
+        launch(self.lib, d.device, self.lib.dn_pipe_stream_push, self.handle, hop.data_ptr(), int(hop.dtype == torch.int16), out.data_ptr(),
+               int(out.dtype == torch.int16), ia_ptr, self.seed, self.stream_id0, d.n_iter, d.momentum)
+        if keep is not None:
+            record_on_stream(keep, d.device)
 
     def push(self, hop: torch.Tensor, init_angles: torch.Tensor | None = None) -> torch.Tensor:
         out = self._out(hop.dtype == torch.int16)
@@ -661,22 +597,17 @@ class PipelinedStream(_Pipe):
         d = self.dn
         H = self.group
         for t, name in ((hops, "hops"), (out, "out")):
-            if t.device != d.device or tuple(t.shape) != (H, self.batch, d.hop) or t.dtype not in (torch.float32, torch.int16) or t.stride(2) != 1 \
-                    or t.stride(1) != d.hop:
-                raise ValueError(f"{name} must be float32 or int16 of shape {(H, self.batch, d.hop)} on {d.device} with contiguous (B, hop) rows")
+            check_tensor(t, name, (H, self.batch, d.hop), PCM, d.device, contiguous=False)
+            if t.stride(2) != 1 or t.stride(1) != d.hop:          # (the H hops themselves may lie apart)
+                raise ValueError(f"{name} must have contiguous (B, hop) rows")
         if check_weights:
             self._bind()
-        ia_ptr, ia_stride, keep = None, 0, None
-        if init_angles is not None:
-            keep = torch.stack([d._angles_ptr(init_angles[h], self.batch)[0] for h in range(H)])
-            ia_ptr, ia_stride = keep.data_ptr(), keep.stride(0)
-        with torch.cuda.device(d.device):
-            cur = torch.cuda.current_stream()
-            self.lib.check(self.lib.dn_pipe_stream_push_group(self.handle, hops.data_ptr(), hops.stride(0), int(hops.dtype == torch.int16), out.data_ptr(),
-                                                              out.stride(0), int(out.dtype == torch.int16), ia_ptr, ia_stride, self.seed,
-                                                              self.stream_id0, d.n_iter, d.momentum, C.c_void_p(cur.cuda_stream)))
-            if keep is not None and not torch.cuda.is_current_stream_capturing():
-                keep.record_stream(cur)
+        keep, ia_ptr = d._angles_ptr(init_angles, H, self.batch)
+        launch(self.lib, d.device, self.lib.dn_pipe_stream_push_group, self.handle, hops.data_ptr(), hops.stride(0), int(hops.dtype == torch.int16),
+               out.data_ptr(), out.stride(0), int(out.dtype == torch.int16), ia_ptr, 0 if keep is None else keep.stride(0), self.seed,
+               self.stream_id0, d.n_iter, d.momentum)
+        if keep is not None:
+            record_on_stream(keep, d.device)
 
     def push_group(self, hops: torch.Tensor, init_angles: torch.Tensor | None = None) -> torch.Tensor:
         out = torch.empty_like(hops)
@@ -689,9 +620,7 @@ class PipelinedStream(_Pipe):
         d = self.dn
         out = torch.empty(self.group, self.batch, d.hop, dtype=torch.int16 if s16 else torch.float32, device=d.device)
         valid = C.c_int32()
-        with torch.cuda.device(d.device):
-            st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
-            self.lib.check(self.lib.dn_pipe_stream_flush_group(self.handle, out.data_ptr(), out.stride(0), int(s16), C.byref(valid), st))
+        launch(self.lib, d.device, self.lib.dn_pipe_stream_flush_group, self.handle, out.data_ptr(), out.stride(0), int(s16), C.byref(valid))
         return out, valid.value
 
     def graph_step(self, hop: torch.Tensor, out: torch.Tensor, init_angles: torch.Tensor | None = None) -> "torch.cuda.CUDAGraph":
@@ -704,23 +633,19 @@ class PipelinedStream(_Pipe):
         if init_angles is not None:
             # the slot buffers for injected phases are allocated by the first parity-mode launch: do that outside the capture
             self._warm_parity()
-        if isinstance(hop, (list, tuple)):             # K separate (B, hop) tensors instead of one (K, B, hop): the same K pushes
-            if not isinstance(out, (list, tuple)) or len(out) != len(hop) or (init_angles is not None and len(init_angles) != len(hop)):
+        listed = isinstance(hop, (list, tuple))
+        if listed or hop.dim() == 3:          # K (B, hop) tensors, or one (K, B, hop): the same K pushes
+            K = len(hop)
+            if isinstance(out, (list, tuple)) != listed or (not listed and out.dim() != 3) or len(out) != K \
+                    or (init_angles is not None and len(init_angles) != K):
                 raise ValueError("K hops need K outputs (and K sets of init_angles)")
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g):
-                for k in range(len(hop)):
-                    self.push_(hop[k], out[k], None if init_angles is None else init_angles[k], check_weights=False)
-            return g
-        if hop.dim() == 3 and (out.dim() != 3 or out.shape[0] != hop.shape[0] or (init_angles is not None and init_angles.shape[0] != hop.shape[0])):
-            raise ValueError("K hops need K outputs (and K sets of init_angles)")
+            steps = [(hop[k], out[k], None if init_angles is None else init_angles[k]) for k in range(K)]
+        else:
+            steps = [(hop, out, init_angles)]
         g = torch.cuda.CUDAGraph()
         with torch.cuda.graph(g):
-            if hop.dim() == 3:
-                for k in range(hop.shape[0]):
-                    self.push_(hop[k], out[k], None if init_angles is None else init_angles[k], check_weights=False)
-            else:
-                self.push_(hop, out, init_angles, check_weights=False)
+            for hop_k, out_k, init_k in steps:
+                self.push_(hop_k, out_k, init_k, check_weights=False)
         return g
 
     def _warm_parity(self) -> None:
@@ -730,12 +655,10 @@ class PipelinedStream(_Pipe):
     def flush(self, s16: bool = False) -> torch.Tensor:
         """Drains the pipe: the hops still in flight, ``(B, depth * hop_length)`` (zeros where nothing was pending)."""
         outs = []
-        with torch.cuda.device(self.dn.device):
-            st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
-            for _ in range(self.depth):
-                out = self._out(s16)
-                self.lib.check(self.lib.dn_pipe_stream_flush(self.handle, out.data_ptr(), int(s16), self.dn.n_iter, self.dn.momentum, st))
-                outs.append(out)
+        for _ in range(self.depth):
+            out = self._out(s16)
+            launch(self.lib, self.dn.device, self.lib.dn_pipe_stream_flush, self.handle, out.data_ptr(), int(s16), self.dn.n_iter, self.dn.momentum)
+            outs.append(out)
         return outs[0] if len(outs) == 1 else torch.cat(outs, dim=1)
 
     def state(self):
@@ -745,9 +668,7 @@ class PipelinedStream(_Pipe):
         ring = torch.empty(self.batch, d.n_fft, dtype=torch.float32, device=d.device)
         ola = torch.empty_like(ring)
         hx = torch.empty(self.batch, d.model.latent_size, d.num_compressed_bins, dtype=torch.float32, device=d.device)
-        with torch.cuda.device(d.device):
-            st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
-            self.lib.check(self.lib.dn_pipe_stream_get_state(self.handle, ring.data_ptr(), ola.data_ptr(), hx.data_ptr(), st))
+        launch(self.lib, d.device, self.lib.dn_pipe_stream_get_state, self.handle, ring.data_ptr(), ola.data_ptr(), hx.data_ptr())
         return ring, ola, hx, self.counters()[1]
 
     def load_state(self, ring: torch.Tensor, ola: torch.Tensor, hx: torch.Tensor, frames: int = 0) -> None:
@@ -755,9 +676,7 @@ class PipelinedStream(_Pipe):
         for t in (ring, ola, hx):
             if t.device != self.dn.device or t.dtype != torch.float32 or not t.is_contiguous():
                 raise ValueError("state tensors must be contiguous float32 on the denoiser's device")
-        with torch.cuda.device(self.dn.device):
-            st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
-            self.lib.check(self.lib.dn_pipe_stream_set_state(self.handle, ring.data_ptr(), ola.data_ptr(), hx.data_ptr(), int(frames), st))
+        launch(self.lib, self.dn.device, self.lib.dn_pipe_stream_set_state, self.handle, ring.data_ptr(), ola.data_ptr(), hx.data_ptr(), int(frames))
 
 
 class HostFedStream(PipelinedStream):
@@ -786,23 +705,21 @@ class HostFedStream(PipelinedStream):
         self._in_ptr = [t.data_ptr() for t in self._pin_in]
         self._out_ptr = [t.data_ptr() for t in self._pin_out]
         self._nbytes = self._pin_in[0].numel() * self._pin_in[0].element_size()
-        self._dtype = dt
+        self._shape, self._dtypes = (batch, denoiser.hop), (dt,)          # what push takes
         self._s16 = int(s16)
         self._n = 0                # pushes made
         self._taken = 0            # results handed out
         self._ticket = C.c_uint64()
+        self._after = (C.byref(self._ticket),)          # dn_pipe_stream_push_host takes the ticket behind its stream
 
     def push(self, hop: torch.Tensor, copy: bool = True) -> torch.Tensor:
         d = self.dn
-        if hop.dtype != self._dtype or hop.device.type != "cpu" or tuple(hop.shape) != (self.batch, d.hop) or not hop.is_contiguous():
-            raise ValueError(f"hop must be a contiguous CPU tensor {self._dtype} of shape {(self.batch, d.hop)}")
+        check_tensor(hop, "hop", self._shape, self._dtypes, "cpu")
         k = self._n % self.RING
         # ring slot k was last used by push n - RING: its upload finished before the result of push n - RING was handed out, LAG pushes ago
         C.memmove(self._in_ptr[k], hop.data_ptr(), self._nbytes)
-        with torch.cuda.device(d.device):
-            st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
-            self.lib.check(self.lib.dn_pipe_stream_push_host(self.handle, self._in_ptr[k], self._s16, self._out_ptr[k], self._s16,
-                                                             self.seed, self.stream_id0, d.n_iter, d.momentum, self._hflags, st, C.byref(self._ticket)))
+        launch(self.lib, d.device, self.lib.dn_pipe_stream_push_host, self.handle, self._in_ptr[k], self._s16, self._out_ptr[k], self._s16,
+               self.seed, self.stream_id0, d.n_iter, d.momentum, self._hflags, after=self._after)
         self._n += 1
         if self._n <= self.LAG:
             return torch.zeros_like(self._pin_out[0])
@@ -1011,10 +928,10 @@ class DenoiserStream:
         self.filled = 0          # samples accepted so far, saturating at n_fft - hop (priming)
         self.hops = 0
 
-    def push(self, chunk: torch.Tensor, init_angles_per_hop=None) -> torch.Tensor:
+    def _accept(self, chunk: torch.Tensor) -> int:
+        """appends ``chunk`` (B, n) to the samples waiting, fills the ring while the streams are priming; -> the whole hops now waiting"""
         d = self.dn
-        if chunk.device != d.device or chunk.dtype != torch.float32 or chunk.shape[0] != self.batch:
-            raise ValueError("chunk must be float32 (B, n) on the denoiser's device")
+        check_tensor(chunk, "chunk", (self.batch, chunk.shape[-1]), (torch.float32,), d.device, contiguous=False)          # (B, n), any n
         self.pending = torch.cat([self.pending, chunk], dim=1)
         prime = d.n_fft - d.hop
         if self.filled < prime:                  # the first frame needs n_fft samples: fill ring[hop:] first
@@ -1022,24 +939,24 @@ class DenoiserStream:
             self.ring[:, d.hop + self.filled: d.hop + self.filled + take] = self.pending[:, :take]
             self.pending = self.pending[:, take:]
             self.filled += take
+        return self.pending.shape[1] // d.hop if self.filled == prime else 0
+
+    def push(self, chunk: torch.Tensor, init_angles_per_hop=None) -> torch.Tensor:
+        d = self.dn
+        n_hops = self._accept(chunk)
         outs = []
         ws = d._workspace(self.batch)
         model_h = d.model._native(d.device)
-        i = 0
-        while self.filled == prime and self.pending.shape[1] >= d.hop:
+        for i in range(n_hops):
             hop_in = self.pending[:, :d.hop].contiguous()
             self.pending = self.pending[:, d.hop:]
             hop_out = torch.empty(self.batch, d.hop, dtype=torch.float32, device=d.device)
-            ia = None if init_angles_per_hop is None else init_angles_per_hop[i]
-            keep, ia_ptr = d._angles_ptr(ia, self.batch)
-            with torch.cuda.device(d.device):
-                st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
-                d.lib.check(d.lib.dn_stream_step(model_h, d.plan.handle, hop_in.data_ptr(), self.ring.data_ptr(), self.ola.data_ptr(),
-                                                 self.hx.data_ptr(), hop_out.data_ptr(), ia_ptr, self.seed + self.hops, self.stream_id0,
-                                                 d.n_iter, d.momentum, ws.data_ptr(), self.batch, d._flags(), st))
+            keep, ia_ptr = d._angles_ptr(None if init_angles_per_hop is None else init_angles_per_hop[i], self.batch)
+            launch(d.lib, d.device, d.lib.dn_stream_step, model_h, d.plan.handle, hop_in.data_ptr(), self.ring.data_ptr(), self.ola.data_ptr(),
+                   self.hx.data_ptr(), hop_out.data_ptr(), ia_ptr, self.seed + self.hops, self.stream_id0, d.n_iter, d.momentum, ws.data_ptr(),
+                   self.batch, d._flags())
             outs.append(hop_out)
             self.hops += 1
-            i += 1
         if not outs:
             return torch.zeros(self.batch, 0, dtype=torch.float32, device=d.device)
         return torch.cat(outs, dim=1)
@@ -1050,16 +967,7 @@ class DenoiserStream:
         Griffin-Lim chains of all hops side by side -- in tiles of at most ``frame_cap`` frames (streams x hops; default: the constructor's
         ``clip_frame_cap``, else ``Denoiser.CLIP_FRAME_CAP``)."""
         d = self.dn
-        if chunk.device != d.device or chunk.dtype != torch.float32 or chunk.shape[0] != self.batch:
-            raise ValueError("chunk must be float32 (B, n) on the denoiser's device")
-        self.pending = torch.cat([self.pending, chunk], dim=1)
-        prime = d.n_fft - d.hop
-        if self.filled < prime:
-            take = min(prime - self.filled, self.pending.shape[1])
-            self.ring[:, d.hop + self.filled: d.hop + self.filled + take] = self.pending[:, :take]
-            self.pending = self.pending[:, take:]
-            self.filled += take
-        n_hops = self.pending.shape[1] // d.hop if self.filled == prime else 0
+        n_hops = self._accept(chunk)
         if n_hops == 0:
             return torch.zeros(self.batch, 0, dtype=torch.float32, device=d.device)
         hops_in = self.pending[:, :n_hops * d.hop].contiguous()

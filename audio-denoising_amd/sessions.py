@@ -28,6 +28,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._glue import PCM, check_tensor, launch, stream_ptr
 
 # the record layout of include/dn_denoise.h (DN_SESS_RECORD_MAGIC, DN_SESS_RECORD_VERSION, dn_session_record_header)
 RECORD_MAGIC = 0x52534E44
@@ -230,25 +231,22 @@ class RateBank:
         return ids, ridx
 
     def _check(self, t, what, dtypes, rows):
-        if t.device != self.device or t.dtype not in dtypes or t.dim() != 2 or t.shape[0] != rows or not t.is_contiguous():
-            raise ValueError(f"{what} must be contiguous {' or '.join(str(d) for d in dtypes)} of {rows} rows on {self.device}")
+        check_tensor(t, what, (rows, None), dtypes, self.device)
 
     def ingest(self, slots, rate_idx, state_in: torch.Tensor, x: torch.Tensor, hop_in: torch.Tensor | None = None) -> torch.Tensor:
         """x (n, W) float32 or int16 at each row's rate -> hop_in (n, hop) float32 at the plan's; state_in (capacity, stride) advances"""
         ids, ridx = self._lists(slots, rate_idx)
         n = ids.size
-        self._check(x, "x", (torch.float32, torch.int16), n)
+        self._check(x, "x", PCM, n)
         self._check(state_in, "state_in", (torch.float32,), state_in.shape[0])
         if hop_in is None:
             hop_in = torch.empty(n, self.hop, dtype=torch.float32, device=self.device)
         self._check(hop_in, "hop_in", (torch.float32,), n)
         if state_in.shape[1] != self.stride[0] or hop_in.shape[1] != self.hop:
             raise ValueError(f"state_in rows are {self.stride[0]} floats, hop_in rows {self.hop}")
-        with torch.cuda.device(self.device):
-            self.lib.check(self.lib.dn_ratebank_ingest(self.handle, ids.ctypes.data_as(C.c_void_p), ridx.ctypes.data_as(C.c_void_p), n,
-                                                       state_in.shape[0], state_in.data_ptr(), x.data_ptr() if n else None,
-                                                       int(x.dtype == torch.int16), x.shape[1], hop_in.data_ptr() if n else None,
-                                                       C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)))
+        launch(self.lib, self.device, self.lib.dn_ratebank_ingest, self.handle, ids.ctypes.data_as(C.c_void_p), ridx.ctypes.data_as(C.c_void_p), n,
+               state_in.shape[0], state_in.data_ptr(), x.data_ptr() if n else None, int(x.dtype == torch.int16), x.shape[1],
+               hop_in.data_ptr() if n else None)
         return hop_in
 
     def emit(self, slots, rate_idx, state_out: torch.Tensor, hop_out: torch.Tensor, y: torch.Tensor) -> torch.Tensor:
@@ -256,15 +254,13 @@ class RateBank:
         ids, ridx = self._lists(slots, rate_idx)
         n = ids.size
         self._check(hop_out, "hop_out", (torch.float32,), n)
-        self._check(y, "y", (torch.float32, torch.int16), n)
+        self._check(y, "y", PCM, n)
         self._check(state_out, "state_out", (torch.float32,), state_out.shape[0])
         if state_out.shape[1] != self.stride[1] or hop_out.shape[1] != self.hop:
             raise ValueError(f"state_out rows are {self.stride[1]} floats, hop_out rows {self.hop}")
-        with torch.cuda.device(self.device):
-            self.lib.check(self.lib.dn_ratebank_emit(self.handle, ids.ctypes.data_as(C.c_void_p), ridx.ctypes.data_as(C.c_void_p), n,
-                                                     state_out.shape[0], state_out.data_ptr(), hop_out.data_ptr() if n else None,
-                                                     y.data_ptr() if n else None, int(y.dtype == torch.int16), y.shape[1],
-                                                     C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)))
+        launch(self.lib, self.device, self.lib.dn_ratebank_emit, self.handle, ids.ctypes.data_as(C.c_void_p), ridx.ctypes.data_as(C.c_void_p), n,
+               state_out.shape[0], state_out.data_ptr(), hop_out.data_ptr() if n else None, y.data_ptr() if n else None,
+               int(y.dtype == torch.int16), y.shape[1])
         return y
 
 
@@ -297,7 +293,7 @@ class SessionPool:
         self.bank = RateBank(d.sample_rate, d.hop, self.rates, d.device, lib=self.lib) if self.rates else None
         self._adapt = self.bank.new_state(self.capacity) if self.bank else None          # (state_in, state_out) [capacity][stride]
         # (samples in, samples out) of a hop by rate index, the plan's rate last
-        self._chunks = np.array([[g["chunk_in"], g["chunk_out"]] for g in (self.bank._geo if self.bank else [])] + [[self.hop, self.hop]])
+        self._chunks = np.array([[g["chunk_in"], g["chunk_out"]] for g in (self.bank.geometry(r) for r in self.rates)] + [[self.hop, self.hop]])
 
     def _create(self, capacity: int):
         handle = C.c_void_p()
@@ -310,7 +306,8 @@ class SessionPool:
 
     # ------------------------------------------------------------------ slot and device layer
     def _stream(self):
-        return C.c_void_p(torch.cuda.current_stream(self.dn.device).cuda_stream)
+        """the pointer of the pool's current stream, for a caller that makes a ``dn_sessions_*`` call of its own on the pool's handle"""
+        return stream_ptr(self.dn.device)
 
     def _ids(self, slots) -> np.ndarray:
         return np.ascontiguousarray(np.asarray(slots, dtype=np.int64).reshape(-1).astype(np.int32))
@@ -326,8 +323,7 @@ class SessionPool:
         slot = int(free[0])
         ids = self._ids([slot])
         sid = None if stream_id is None else (C.c_uint64 * 1)(int(stream_id))
-        with torch.cuda.device(self.dn.device):
-            self.lib.check(self.lib.dn_sessions_open(self.handle, ids.ctypes.data_as(C.c_void_p), 1, sid, self._stream()))
+        launch(self.lib, self.dn.device, self.lib.dn_sessions_open, self.handle, ids.ctypes.data_as(C.c_void_p), 1, sid)
         self._open[slot] = True
         self._pushes[slot] = 0
         self._queue[slot] = np.zeros(0, dtype=np.float32)
@@ -353,8 +349,7 @@ class SessionPool:
     def counters(self, slot: int):
         """(frames since the open, pushes counted up to n_fft/hop - 1) of a slot.  Synchronises the current stream."""
         f, p = C.c_uint64(), C.c_int32()
-        with torch.cuda.device(self.dn.device):
-            self.lib.check(self.lib.dn_sessions_get_counters(self.handle, int(slot), C.byref(f), C.byref(p), self._stream()))
+        launch(self.lib, self.dn.device, self.lib.dn_sessions_get_counters, self.handle, int(slot), C.byref(f), C.byref(p))
         return f.value, p.value
 
     def push(self, slots, hops: torch.Tensor, out: torch.Tensor | None = None, init_angles: torch.Tensor | None = None) -> torch.Tensor:
@@ -371,21 +366,17 @@ class SessionPool:
     def _push(self, ids, hops, out, init_angles=None) -> torch.Tensor:
         d = self.dn
         n = ids.size
-        if hops.device != d.device or hops.dtype not in (torch.float32, torch.int16) or tuple(hops.shape) != (n, self.hop) \
-                or not hops.is_contiguous():
-            raise ValueError(f"hops must be contiguous float32 or int16 of shape {(n, self.hop)} on {d.device}")
+        check_tensor(hops, "hops", (n, self.hop), PCM, d.device)
         if out is None:
             out = torch.empty(n, self.hop, dtype=hops.dtype, device=d.device)
-        elif out.device != d.device or out.dtype not in (torch.float32, torch.int16) or tuple(out.shape) != (n, self.hop) \
-                or not out.is_contiguous():
-            raise ValueError(f"out must be contiguous float32 or int16 of shape {(n, self.hop)} on {d.device}")
+        else:
+            check_tensor(out, "out", (n, self.hop), PCM, d.device)
         if d.model._native_owner(d.device) is not self._owner or d._flags() != self._flags:
             raise RuntimeError("the model's weights or conv_precision changed after the session pool was created; create a new pool")
         keep, ia_ptr = d._angles_ptr(init_angles, n)
-        with torch.cuda.device(d.device):
-            self.lib.check(self.lib.dn_sessions_push(self.handle, ids.ctypes.data_as(C.c_void_p), n, hops.data_ptr() if n else None,
-                                                     int(hops.dtype == torch.int16), out.data_ptr() if n else None,
-                                                     int(out.dtype == torch.int16), ia_ptr, self.seed, d.n_iter, d.momentum, self._stream()))
+        launch(self.lib, d.device, self.lib.dn_sessions_push, self.handle, ids.ctypes.data_as(C.c_void_p), n, hops.data_ptr() if n else None,
+               int(hops.dtype == torch.int16), out.data_ptr() if n else None, int(out.dtype == torch.int16), ia_ptr, self.seed, d.n_iter,
+               d.momentum)
         self._pushes[ids] += 1
         return out
 
@@ -399,7 +390,7 @@ class SessionPool:
         k = self._rate[int(slot)]
         if k < 0:
             return self.hop, self.hop
-        g = self.bank._geo[k]
+        g = self.bank.geometry(self.rates[k])
         return g["chunk_in"], g["chunk_out"]
 
     def delay(self, slot: int) -> int:
@@ -408,7 +399,7 @@ class SessionPool:
         k = self._rate[int(slot)]
         if k < 0:
             return 0
-        g = self.bank._geo[k]
+        g = self.bank.geometry(self.rates[k])
         return g["delay_in"] * self.rates[k] // self.geometry["sample_rate"] + g["delay_out"]
 
     def push_rated(self, slots, x: torch.Tensor, out: torch.Tensor | None = None) -> torch.Tensor:
@@ -424,14 +415,11 @@ class SessionPool:
         ch = self._chunks[ridx]          # (index -1, the plan's rate: the last row)
         w_in, w_out = (int(ch[:, 0].max()), int(ch[:, 1].max())) if n else (0, 0)
         dev = self.dn.device
-        if x.device != dev or x.dtype not in (torch.float32, torch.int16) or x.dim() != 2 or x.shape[0] != n or x.shape[1] < w_in \
-                or not x.is_contiguous():
-            raise ValueError(f"x must be contiguous float32 or int16 of shape ({n}, W >= {w_in}) on {dev}")
+        check_tensor(x, "x", (n, None), PCM, dev, min_width=w_in)
         if out is None:
             out = torch.empty(n, w_out, dtype=x.dtype, device=dev)
-        elif out.device != dev or out.dtype not in (torch.float32, torch.int16) or out.dim() != 2 or out.shape[0] != n or out.shape[1] < w_out \
-                or not out.is_contiguous():
-            raise ValueError(f"out must be contiguous float32 or int16 of shape ({n}, W >= {w_out}) on {dev}")
+        else:
+            check_tensor(out, "out", (n, None), PCM, dev, min_width=w_out)
         if n == 0:
             return out
         hop_in = self.bank.ingest(ids, ridx, self._adapt[0], x)
@@ -509,8 +497,7 @@ class SessionPool:
         n = ids.size
         rec = torch.empty(n, self.record_bytes, dtype=torch.uint8, device=self.dn.device)
         if n:
-            with torch.cuda.device(self.dn.device):
-                self.lib.check(self.lib.dn_sessions_export(self.handle, ids.ctypes.data_as(C.c_void_p), n, rec.data_ptr(), self._stream()))
+            launch(self.lib, self.dn.device, self.lib.dn_sessions_export, self.handle, ids.ctypes.data_as(C.c_void_p), n, rec.data_ptr())
         return SessionState(rec, self.geometry, self.seed, [self._queue[int(s)].copy() for s in ids], self._pushes[ids], **self._export_rates(ids))
 
     def _export_rates(self, ids) -> dict:
@@ -519,9 +506,10 @@ class SessionPool:
             return {}
         idx = torch.from_numpy(ids.astype(np.int64)).to(self.dn.device)
         rows = [t.index_select(0, idx).cpu().numpy() for t in self._adapt]
-        hist = [(0, 0) if k < 0 else (self.bank._geo[k]["hist_in"], self.bank._geo[k]["hist_out"]) for k in self._rate[ids]]
-        return dict(rates=[self.sample_rate(s) for s in ids], adapter_in=[rows[0][i, :h[0]] for i, h in enumerate(hist)],
-                    adapter_out=[rows[1][i, :h[1]] for i, h in enumerate(hist)])
+        rates = [self.sample_rate(s) for s in ids]
+        geo = [self.bank.geometry(r) for r in rates]          # (no state floats at the plan's rate)
+        return dict(rates=rates, adapter_in=[rows[0][i, :g["hist_in"]] for i, g in enumerate(geo)],
+                    adapter_out=[rows[1][i, :g["hist_out"]] for i, g in enumerate(geo)])
 
     def _check_rates(self, rates):
         """the rate index of each session of a state in THIS pool (None: no session has a rate); ValueError when the pool lacks one"""
@@ -571,9 +559,8 @@ class SessionPool:
         if n == 0:
             return []
         rec = state.records.to(self.dn.device).contiguous()
-        with torch.cuda.device(self.dn.device):
-            self.lib.check(self.lib.dn_sessions_import(self.handle, ids.ctypes.data_as(C.c_void_p), n, rec.data_ptr(),
-                                                       None if sids is None else sids.ctypes.data_as(C.c_void_p), self._stream()))
+        launch(self.lib, self.dn.device, self.lib.dn_sessions_import, self.handle, ids.ctypes.data_as(C.c_void_p), n, rec.data_ptr(),
+               None if sids is None else sids.ctypes.data_as(C.c_void_p))
         self._open[ids] = True
         self._pushes[ids] = state.host_pushes
         for k, s in enumerate(ids):
@@ -616,10 +603,8 @@ class SessionPool:
             if live.size:
                 ids = self._ids(live)
                 rec = torch.empty(ids.size, self.record_bytes, dtype=torch.uint8, device=self.dn.device)
-                with torch.cuda.device(self.dn.device):
-                    st = self._stream()
-                    self.lib.check(self.lib.dn_sessions_export(self.handle, ids.ctypes.data_as(C.c_void_p), ids.size, rec.data_ptr(), st))
-                    self.lib.check(self.lib.dn_sessions_import(handle, ids.ctypes.data_as(C.c_void_p), ids.size, rec.data_ptr(), None, st))
+                launch(self.lib, self.dn.device, self.lib.dn_sessions_export, self.handle, ids.ctypes.data_as(C.c_void_p), ids.size, rec.data_ptr())
+                launch(self.lib, self.dn.device, self.lib.dn_sessions_import, handle, ids.ctypes.data_as(C.c_void_p), ids.size, rec.data_ptr(), None)
         except Exception:
             fin()
             raise

@@ -24,6 +24,7 @@ import torch
 from torch import nn
 
 from . import _lib
+from ._glue import PCM, check_tensor, launch
 
 _N_FFTS = (512, 1024, 1536)   # the one-wave FFT kernels: 256 = 4*4*4*4, 512 = 8*8*8 and 768 = 4*4*4*12 complex points (hop = n_fft/2)
 
@@ -87,15 +88,9 @@ class DspPlan:
         return int(self.lib.dn_workspace_bytes_ex(self.handle, batch, flags))
 
 
-def _stream_ptr(device):
-    return C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
-
-
-def _require(t: torch.Tensor, dtype, what: str):
-    if not t.is_cuda:
-        raise RuntimeError(f"{what}: expected a CUDA tensor (this package has no CPU path)")
-    if t.dtype != dtype:
-        raise TypeError(f"{what}: expected {dtype}, got {t.dtype}")
+def _require(t: torch.Tensor, dtypes, what: str):
+    """the argument check of a transform: a CUDA tensor (else RuntimeError) of one of ``dtypes`` (else TypeError), any shape and strides"""
+    check_tensor(t, what, None, dtypes, "cuda", RuntimeError, TypeError, contiguous=False)
 
 
 class _PlanModule(nn.Module):
@@ -153,7 +148,7 @@ class Spectrogram(_PlanModule):
         return dict(sample_rate=0, n_fft=self.n_fft, hop=self.hop_length, n_mels=0, window=self.window)
 
     def forward(self, waveform: torch.Tensor) -> torch.Tensor:
-        _require(waveform, torch.float32, "Spectrogram")
+        _require(waveform, (torch.float32,), "Spectrogram")
         L = waveform.shape[-1]
         if L <= self.n_fft // 2:
             raise RuntimeError(f"reflect padding needs more than n_fft/2 = {self.n_fft // 2} samples (as torch.stft); got {L}")
@@ -163,11 +158,10 @@ class Spectrogram(_PlanModule):
         B = x.shape[0]
         plan = self.plan(x.device)
         spec = torch.empty(B, T, plan.n_stft, 2, dtype=torch.float32, device=x.device)
-        with torch.cuda.device(x.device):
-            if L == self.n_fft:
-                plan.lib.check(plan.lib.dn_stft(plan.handle, x.data_ptr(), spec.data_ptr(), B, 0, _stream_ptr(x.device)))
-            else:
-                plan.lib.check(plan.lib.dn_stft_general(plan.handle, x.data_ptr(), spec.data_ptr(), None, B, L, _stream_ptr(x.device)))
+        if L == self.n_fft:
+            launch(plan.lib, x.device, plan.lib.dn_stft, plan.handle, x.data_ptr(), spec.data_ptr(), B, 0)
+        else:
+            launch(plan.lib, x.device, plan.lib.dn_stft_general, plan.handle, x.data_ptr(), spec.data_ptr(), None, B, L)
         out = torch.view_as_complex(spec).reshape(lead + (T, plan.n_stft)).transpose(-1, -2)
         if self.power is None:
             return out
@@ -199,7 +193,7 @@ class MelScale(_PlanModule):
         return dict(sample_rate=self.sample_rate, n_fft=n_fft, hop=n_fft // 2, n_mels=self.n_mels, fb=self.fb)
 
     def forward(self, specgram: torch.Tensor) -> torch.Tensor:
-        _require(specgram, torch.float32, "MelScale")
+        _require(specgram, (torch.float32,), "MelScale")
         if specgram.shape[-2] != self.n_stft:
             raise RuntimeError(f"expected {self.n_stft} frequency bins, got {specgram.shape[-2]}")
         rows = _rows_layout(specgram)                      # [.., T, K]
@@ -207,8 +201,7 @@ class MelScale(_PlanModule):
         B = rows.numel() // (T * self.n_stft)
         plan = self.plan(rows.device)
         mel = torch.empty(lead + (T, self.n_mels), dtype=torch.float32, device=rows.device)
-        with torch.cuda.device(rows.device):
-            plan.lib.check(plan.lib.dn_mel_scale(plan.handle, rows.data_ptr(), mel.data_ptr(), B, T, _stream_ptr(rows.device)))
+        launch(plan.lib, rows.device, plan.lib.dn_mel_scale, plan.handle, rows.data_ptr(), mel.data_ptr(), B, T)
         return mel.transpose(-1, -2)
 
 
@@ -235,7 +228,7 @@ class InverseMelScale(_PlanModule):
         return dict(sample_rate=self.sample_rate, n_fft=n_fft, hop=n_fft // 2, n_mels=self.n_mels, fb=self.fb)
 
     def forward(self, melspec: torch.Tensor) -> torch.Tensor:
-        _require(melspec, torch.float32, "InverseMelScale")
+        _require(melspec, (torch.float32,), "InverseMelScale")
         if melspec.shape[-2] != self.n_mels:
             raise ValueError(f"Expected an input with {self.n_mels} mel bins. Found: {melspec.shape[-2]}")
         rows = _rows_layout(melspec)                       # [.., T, M]
@@ -243,8 +236,7 @@ class InverseMelScale(_PlanModule):
         B = rows.numel() // (T * self.n_mels)
         plan = self.plan(rows.device)
         lin = torch.empty(lead + (T, self.n_stft), dtype=torch.float32, device=rows.device)
-        with torch.cuda.device(rows.device):
-            plan.lib.check(plan.lib.dn_invmel(plan.handle, rows.data_ptr(), lin.data_ptr(), B, T, _stream_ptr(rows.device)))
+        launch(plan.lib, rows.device, plan.lib.dn_invmel, plan.handle, rows.data_ptr(), lin.data_ptr(), B, T)
         return lin.transpose(-1, -2)
 
 
@@ -276,7 +268,7 @@ class GriffinLim(_PlanModule):
         return dict(sample_rate=0, n_fft=self.n_fft, hop=self.hop_length, n_mels=0, window=self.window)
 
     def forward(self, specgram: torch.Tensor, init_angles: torch.Tensor | None = None) -> torch.Tensor:
-        _require(specgram, torch.float32, "GriffinLim")
+        _require(specgram, (torch.float32,), "GriffinLim")
         K = self.n_fft // 2 + 1
         T = specgram.shape[-1]
         if self.length is not None and T != 3:
@@ -291,7 +283,7 @@ class GriffinLim(_PlanModule):
         plan = self.plan(rows.device)
         ia_ptr, seed = None, 0
         if init_angles is not None:
-            _require(init_angles, torch.complex64, "GriffinLim init_angles")
+            _require(init_angles, (torch.complex64,), "GriffinLim init_angles")
             if init_angles.shape != specgram.shape:
                 raise ValueError("init_angles must have the shape of the spectrogram")
             ia = torch.view_as_real(_rows_layout(init_angles).resolve_conj()).contiguous()
@@ -303,14 +295,13 @@ class GriffinLim(_PlanModule):
             ia[..., 0] = 1.0
             ia_ptr = ia.data_ptr()
         wave = torch.empty(lead + (self.hop_length * (T - 1),), dtype=torch.float32, device=rows.device)
-        with torch.cuda.device(rows.device):
-            if T == 3:
-                plan.lib.check(plan.lib.dn_griffinlim(plan.handle, rows.data_ptr(), ia_ptr, seed, 0, None, wave.data_ptr(), B,
-                                                      int(self.n_iter), float(self.momentum), _stream_ptr(rows.device)))
-            else:
-                ws = torch.empty(max(1, int(plan.lib.dn_griffinlim_general_workspace_bytes(plan.handle, B, T))), dtype=torch.uint8, device=rows.device)
-                plan.lib.check(plan.lib.dn_griffinlim_general(plan.handle, rows.data_ptr(), ia_ptr, seed, 0, wave.data_ptr(), ws.data_ptr(), B, T,
-                                                              int(self.n_iter), float(self.momentum), 0, _stream_ptr(rows.device)))
+        if T == 3:
+            launch(plan.lib, rows.device, plan.lib.dn_griffinlim, plan.handle, rows.data_ptr(), ia_ptr, seed, 0, None, wave.data_ptr(), B,
+                   int(self.n_iter), float(self.momentum))
+        else:
+            ws = torch.empty(max(1, int(plan.lib.dn_griffinlim_general_workspace_bytes(plan.handle, B, T))), dtype=torch.uint8, device=rows.device)
+            launch(plan.lib, rows.device, plan.lib.dn_griffinlim_general, plan.handle, rows.data_ptr(), ia_ptr, seed, 0, wave.data_ptr(), ws.data_ptr(),
+                   B, T, int(self.n_iter), float(self.momentum), 0)
         return wave
 
 
@@ -331,7 +322,7 @@ class InverseSpectrogram(_PlanModule):
         return dict(sample_rate=0, n_fft=self.n_fft, hop=self.hop_length, n_mels=0, window=self.window)
 
     def forward(self, spectrogram: torch.Tensor, length=None) -> torch.Tensor:
-        _require(spectrogram, torch.complex64, "InverseSpectrogram")
+        _require(spectrogram, (torch.complex64,), "InverseSpectrogram")
         K = self.n_fft // 2 + 1
         T = spectrogram.shape[-1]
         if length is not None and (length != self.n_fft or T != 3):
@@ -343,11 +334,10 @@ class InverseSpectrogram(_PlanModule):
         B = rows.numel() // (T * K * 2)
         plan = self.plan(rows.device)
         wave = torch.empty(lead + (self.hop_length * (T - 1),), dtype=torch.float32, device=rows.device)
-        with torch.cuda.device(rows.device):
-            if T == 3:
-                plan.lib.check(plan.lib.dn_istft(plan.handle, rows.data_ptr(), wave.data_ptr(), B, _stream_ptr(rows.device)))
-            else:
-                plan.lib.check(plan.lib.dn_istft_general(plan.handle, rows.data_ptr(), wave.data_ptr(), B, T, _stream_ptr(rows.device)))
+        if T == 3:
+            launch(plan.lib, rows.device, plan.lib.dn_istft, plan.handle, rows.data_ptr(), wave.data_ptr(), B)
+        else:
+            launch(plan.lib, rows.device, plan.lib.dn_istft_general, plan.handle, rows.data_ptr(), wave.data_ptr(), B, T)
         return wave
 
 
@@ -461,10 +451,7 @@ class Resample(nn.Module):
         return t, stride
 
     def forward(self, waveform: torch.Tensor) -> torch.Tensor:
-        if not waveform.is_cuda:
-            raise RuntimeError("Resample: expected a CUDA tensor (this package has no CPU path)")
-        if waveform.dtype not in (torch.float32, torch.int16):
-            raise TypeError(f"Resample: expected torch.float32 or torch.int16, got {waveform.dtype}")
+        _require(waveform, PCM, "Resample")
         if self.orig_freq == self.new_freq:
             return waveform
         L = waveform.shape[-1]
@@ -475,9 +462,7 @@ class Resample(nn.Module):
             return out
         x, xs = self._rows(waveform)
         s16 = int(waveform.dtype == torch.int16)
-        with torch.cuda.device(waveform.device):
-            self.lib.check(self.lib.dn_resample(self.handle(waveform.device), x.data_ptr(), s16, out.data_ptr(), s16, x.shape[0], L, xs, Ly,
-                                                _stream_ptr(waveform.device)))
+        launch(self.lib, waveform.device, self.lib.dn_resample, self.handle(waveform.device), x.data_ptr(), s16, out.data_ptr(), s16, x.shape[0], L, xs, Ly)
         return out
 
 
@@ -506,10 +491,7 @@ class ResampleStream:
 
     def push(self, chunk: torch.Tensor) -> torch.Tensor:
         r = self.resample
-        if not chunk.is_cuda:
-            raise RuntimeError("ResampleStream: expected a CUDA tensor (this package has no CPU path)")
-        if chunk.dtype not in (torch.float32, torch.int16):
-            raise TypeError(f"ResampleStream: expected torch.float32 or torch.int16, got {chunk.dtype}")
+        _require(chunk, PCM, "ResampleStream")
         if chunk.dim() != 2 or chunk.shape[0] != self.batch or chunk.shape[1] % r.o != 0:
             raise ValueError(f"a push is ({self.batch}, k * {r.o}) samples, whole blocks; got {tuple(chunk.shape)}")
         if chunk.shape[1] == 0:          # nothing arrived (a stream front end that is still priming emits (B, 0)): nothing is owed, the state stays
@@ -523,9 +505,8 @@ class ResampleStream:
         x, xs = Resample._rows(chunk)
         out = torch.empty(self.batch, blocks * r.n, dtype=chunk.dtype, device=chunk.device)
         s16 = int(chunk.dtype == torch.int16)
-        with torch.cuda.device(chunk.device):
-            r.lib.check(r.lib.dn_resample_push(r.handle(chunk.device), self.state.data_ptr(), x.data_ptr(), s16, out.data_ptr(), s16, self.batch, blocks,
-                                               xs, blocks * r.n, _stream_ptr(chunk.device)))
+        launch(r.lib, chunk.device, r.lib.dn_resample_push, r.handle(chunk.device), self.state.data_ptr(), x.data_ptr(), s16, out.data_ptr(), s16,
+               self.batch, blocks, xs, blocks * r.n)
         return out
 
     def flush(self) -> torch.Tensor:
